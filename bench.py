@@ -17,6 +17,14 @@ timed on one GPU with MPVAE_FORCE_DIST=1 to see the fixed costs).
     python bench.py [--gpus N --steps K --warmup W --config c4|c2|c3|c5 --scaling strong|weak]
     torchrun --nproc-per-node N bench.py --gpus N ...
 
+A plain run sets up, warms up, times the K steps and prints one JSON line (the
+roofline in it comes from HIP events of those same steps).  --full adds what
+takes runs of its own after them: the CPU baseline (``cpu_baseline``) and the
+GPU path's ``elbo_rel_err`` on the baseline's slice; both are null without it.
+--dump-outputs DIR writes what the last timed step returned (the 8-tuple of
+``compute_loss`` and, in train mode, every leaf's gradient) as DIR/<name>.npy;
+inputs and Philox keys depend on the arguments alone.
+
 ``python bench.py --gpus N`` (N > 1, no WORLD_SIZE in the environment) starts
 its own N rank processes (mpvae_launch.py) before any GPU call and prints rank
 0's line.  MPVAE_DIST_BACKEND=gloo runs the exchange over gloo instead of RCCL
@@ -188,7 +196,35 @@ def graph_steps(y, leaves, args, warmup, steps):
     for _ in range(steps):
         graph.replay()
     torch.cuda.synchronize()
-    return out, time.perf_counter() - t0
+    return out, time.perf_counter() - t0, leaves
+
+
+OUT_NAMES = ["total", "nll", "nll_x", "c", "c_x", "kl", "indiv_prob", "indiv_prob_label"]
+# --dump-outputs: arrays of more elements than this are written as a fixed,
+# seeded sample of their flattened elements (C5's d r_sqrt_sigma is 128 MB in
+# fp64); 2^21 elements keep every configuration's dump under 64 MB in all
+DUMP_MAX_ELEMS = 1 << 21
+
+
+def dump_outputs(path, out, leaves, train):
+    """What the timed path handed its caller in the last timed step, as
+    <path>/<name>.npy: compute_loss's 8-tuple and, in train mode, the gradient
+    that its backward left on every leaf (grad_<leaf>), in the tensor's own
+    float32 / float64.  Inputs and Philox keys depend on the arguments alone,
+    so two builds run with the same arguments can be compared file by file."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = dict(zip(OUT_NAMES, out))
+    if train:
+        arrays.update({"grad_" + k: leaves[k].grad for k in ORDER})
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float32)
+        if a.size > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).integers(0, a.size, size=DUMP_MAX_ELEMS))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def roofline(times, S_local, B, L, z, steps, gemm, valu=None):
@@ -355,7 +391,14 @@ def main():
     ap.add_argument("--steps", type=int, default=None, help="default: DEFAULT_STEPS[config]")
     ap.add_argument("--warmup", type=int, default=None, help="default: DEFAULT_STEPS[config]")
     ap.add_argument("--config", default="c4", choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    # a plain run sets up, warms up, times the steps and prints its line; --full
+    # adds the legs that take runs of their own after the timed steps: the CPU
+    # baseline (cpu_baseline) and, on its slice, elbo_rel_err of the GPU path
+    ap.add_argument("--full", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (and gradients) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: leave the CPU baseline out")
     ap.add_argument("--cpu-sample-s", type=int, default=2)
     ap.add_argument("--cpu-reps", type=int, default=2)
     ap.add_argument("--gemm", default="f16x3", choices=sorted(PEAKS))
@@ -434,7 +477,7 @@ def main():
         if world > 1 or forced:
             raise SystemExit("--graph runs one process (no collectives in the captured step)")
         del out  # the eager pass's autograd graph
-        out, elapsed = graph_steps(y, leaves, args, cli.warmup, cli.steps)
+        out, elapsed, leaves = graph_steps(y, leaves, args, cli.warmup, cli.steps)
         graph_note = "HIP graph replay of the captured step (ms_per_step, value); roofline " \
                      "kernel times from the eager pass of the same step"
     if dist.is_initialized():
@@ -442,6 +485,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t)
     finite = bool(torch.isfinite(out[0]).item())
+    if cli.dump_outputs and rank == 0:
+        dump_outputs(cli.dump_outputs, out, leaves, cli.mode == "train")
     value = S_total * B * L * cli.steps / elapsed
     prof_key = cli.config if cli.mode == "train" else cli.config + "eval"
     valu, valu_src = pmc_valu(prof_key)
@@ -470,7 +515,7 @@ def main():
                            "blocks the host)"}
 
     cpu, errs = None, None
-    if rank == 0 and world == 1 and not cli.no_cpu_baseline and cli.mode == "train":
+    if cli.full and rank == 0 and world == 1 and not cli.no_cpu_baseline and cli.mode == "train":
         S_cpu = max(1, min(cli.cpu_sample_s, S))
         cpu, errs = cpu_baseline(L, z, B, d, S_cpu, cli.cpu_reps, device)
 

@@ -49,7 +49,7 @@ tests)
   done
   ;;
 bench)
-  b c4_bench
+  b c4_bench --full
   b c4eval_bench --mode eval --no-cpu-baseline
   b c2_bench --config c2 --no-cpu-baseline
   b c2graph_bench --config c2 --graph --no-cpu-baseline

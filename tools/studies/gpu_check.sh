@@ -9,6 +9,7 @@ ok_or_fail() {  # rc, step
   if [ "$rc" -ne 0 ] && [ "$rc" -ne 1 ]; then echo "stopping after $2 (rc=$rc)"; exit "$rc"; fi
 }
 STEPS="${STEPS:-tests smoke bench}"
+BENCH_ARGS="${BENCH_ARGS:---full}"   # the whole record: CPU baseline and elbo_rel_err too
 for s in $STEPS; do
   case $s in
     tests) timeout -k 10 900 python -m pytest tests -m gpu -q -rf ${PYTEST_ARGS} > gpurun_out/pytest_gpu.log 2>&1
