@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MPV_ABI_VERSION 10 /* 4: device-memory Philox keys (mpv_noise_philox*_dev);
+#define MPV_ABI_VERSION 11 /* 4: device-memory Philox keys (mpv_noise_philox*_dev);
                               5: T rows padded to roundup(L, 4) floats;
                               6: mpv_linear (the VAE's Linear layers); mpv_bwd_args
                                  dR64 and kl;
@@ -48,7 +48,8 @@ extern "C" {
                                  combine folded into the finalize launch); only
                                  the live slots of gscal are read (mpv_kl_bwd_args
                                  .live); mpv_noise_philox_f16_split;
-                                 mpv_final_args.seed_advance */
+                                 mpv_final_args.seed_advance
+                             11: mpv_curve_metrics (validation AUC / AUPR / FDR) */
 
 enum mpv_status { MPV_OK = 0, MPV_EINVAL = 1, MPV_ELAUNCH = 2 };
 enum mpv_dtype { MPV_F32 = 0, MPV_F64 = 1 };
@@ -428,7 +429,9 @@ int mpv_adam_finish(const mpv_adam_finish_args* args, void* stream);
  * HIP events on the launch stream (bench.py's per-kernel roofline timing).
  * Kernel names: noise_philox, probit_fwd, fwd_combine, finalize, bwd_coef,
  * bwd_elem, dR_gemm, sum_slabs, convert, bstat_combine, reparam_fwd,
- * reparam_bwd, kl_bwd, linear, adam, adam_finish.  Query synchronises the recorded events. */
+ * reparam_bwd, kl_bwd, linear, adam, adam_finish, label_weights, fair_fwd,
+ * fair_bwd, metrics, curve_keys, curve_sort (the LDS chunk sort), curve_merge
+ * (the merge passes), curve_pass, curve_agg.  Query synchronises the recorded events. */
 int mpv_timing_enable(int on);
 int mpv_timing_reset(void);
 int mpv_timing_query(const char* kernel, int64_t* launches, double* total_ms);
@@ -490,6 +493,33 @@ int mpv_fair_bwd(const mpv_fair_args* args, const double* gout, float* g_label_z
 size_t mpv_metrics_workspace_bytes(int64_t B, int64_t L);
 int mpv_train_metrics(const float* pred, const float* target, int64_t B, int64_t L,
                       float threshold, double* out, void* workspace, size_t workspace_bytes,
+                      void* stream);
+
+/* ---- Validation metrics: evals.compute_metrics(pred, target, thr,
+ * all_metrics=True) (evals.py:129-175; curves.hip) ---------------------------
+ * Per label, over the whole validation split (N rows): ROC AUC
+ * (roc_auc_score), the area under the precision-recall curve
+ * (precision_recall_curve + auc) and the recall at the lowest threshold whose
+ * FDR = 1 - precision is <= 0.5 (compute_fdr), from one descending sort of the
+ * label's scores; then mean, median and population variance of each over the
+ * labels whose value is not NaN.  auc[l] is NaN for a label with one class
+ * only; aupr and fdr are always defined.  fp64, fixed-order sums: the results
+ * do not depend on `chunk` or on which sort path ran. */
+typedef struct mpv_curve_args {
+  const float* pred;   /* (N, L) scores */
+  const float* target; /* (N, L) exact 0 / 1 */
+  int64_t N, L;        /* N < 2^31, L <= 4096 */
+  int64_t chunk;       /* keys one workgroup sorts in LDS: 0 = the default (4096), else a
+                          power of two in [64, 4096]; N > chunk adds global merge passes */
+  double* auc;         /* (L) out */
+  double* aupr;        /* (L) out */
+  double* fdr;         /* (L) out */
+  double* agg;         /* (9) out: mean, median, var of auc; of aupr; of fdr */
+} mpv_curve_args;
+
+/* 0 for a bad shape or chunk. */
+size_t mpv_curves_workspace_bytes(int64_t N, int64_t L, int64_t chunk);
+int mpv_curve_metrics(const mpv_curve_args* args, void* workspace, size_t workspace_bytes,
                       void* stream);
 
 #ifdef __cplusplus

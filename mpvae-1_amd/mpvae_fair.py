@@ -28,6 +28,23 @@ host fallback.  Differences from the reference, none of them numeric:
   the reference's numpy scalars); p@k ties go to the larger label index
   (numpy's default argsort is not stable, so the reference's tie order is
   implementation-defined).
+
+The validation form, ``compute_metrics(..., all_metrics=True)`` and
+``best_threshold_metrics`` (the threshold sweep of validate_mpvae,
+fairsoft_train.py:400-416), runs in csrc/curves.hip: one descending sort per
+label of the whole validation split, then AUC / AUPR / FDR from per-run totals.
+Differences from the reference:
+* ``allAUC`` / ``allAUPR`` / ``allFDR`` always have length L; a label the
+  metric is undefined for (AUC of a one-class label) holds NaN where the
+  reference drops the entry;
+* mean, median and variance skip the NaN labels.  That is what the reference's
+  ``try / except ValueError`` did with the scikit-learn it was written for;
+  a scikit-learn whose ``roc_auc_score`` returns NaN for a one-class label
+  (with a warning) instead of raising makes the reference's own mean NaN;
+* ``best_threshold_metrics`` reduces over the thresholds with torch.amax, which
+  propagates NaN: a metric that is NaN at any threshold (ebF1 or maF1 with no
+  defined term, meanAUC with no two-class label) comes back NaN, where
+  Python's max / min keep or drop it depending on the order.
 """
 import ctypes
 
@@ -243,19 +260,18 @@ def fairness_penalty(indiv_prob_label, indiv_prob, input_label, sensitive_feat, 
 
 
 METRIC_KEYS = ["ACC", "HA", "ebF1", "miF1", "maF1", "p_at_1", "p_at_3", "p_at_5"]
+CURVE_KEYS = ["meanAUC", "medianAUC", "varAUC", "meanAUPR", "medianAUPR", "varAUPR", "meanFDR",
+              "medianFDR", "varFDR"]
+CURVE_CHUNK = 4096  # keys one workgroup sorts in LDS by default (curves.hip kCurveChunk)
+# validate_mpvae's sweep and the metrics it keeps (train.py:22-24, restated)
+THRESHOLDS = [0.01, 0.02, 0.03, 0.04, 0.05, 0.06, 0.07, 0.08, 0.09, 0.10, 0.15, 0.20, 0.25, 0.30,
+              0.35, 0.40, 0.45, 0.50, 0.55, 0.60, 0.65, 0.70, 0.75, 0.80, 0.85, 0.90, 0.95]
+METRICS = ["ACC", "HA", "ebF1", "miF1", "maF1", "meanAUC", "medianAUC", "meanAUPR", "medianAUPR",
+           "meanFDR", "medianFDR", "p_at_1", "p_at_3", "p_at_5"]
 
 
-def compute_metrics(predictions, targets, threshold, all_metrics=False):
-    """evals.compute_metrics (evals.py:178-238) for the per-step call
-    (all_metrics=False): the same keys, the AUC/AUPR/FDR entries 0 as in the
-    reference; values are 0-d fp64 device tensors."""
-    if all_metrics:
-        raise NotImplementedError("all_metrics=True (per-label AUC/AUPR/FDR curves, evaluation "
-                                  "only) is not on the device path; use the reference's "
-                                  "evals.compute_metrics on host arrays")
-    H.require_gpu(predictions, targets)
-    p = predictions.detach().contiguous().float()
-    t = targets.detach().contiguous().float()
+def _train_metrics(p, t, threshold):
+    """mpv_train_metrics on contiguous fp32 device tensors -> (8,) fp64."""
     B, L = p.shape
     lib = H.load_library()
     nbytes = lib.mpv_metrics_workspace_bytes(B, L)
@@ -263,8 +279,70 @@ def compute_metrics(predictions, targets, threshold, all_metrics=False):
     out = torch.empty(8, dtype=torch.float64, device=p.device)
     H.check(lib.mpv_train_metrics(H.ptr(p), H.ptr(t), B, L, float(threshold), H.ptr(out), H.ptr(ws),
                                   nbytes, H.stream_of(p.device)), "mpv_train_metrics")
-    res = {k: out[i] for i, k in enumerate(METRIC_KEYS)}
-    for k in ["meanAUC", "medianAUC", "varAUC", "allAUC", "meanAUPR", "medianAUPR", "varAUPR",
-              "allAUPR", "meanFDR", "medianFDR", "varFDR", "allFDR"]:
-        res[k] = 0
+    return out
+
+
+def curve_metrics(predictions, targets, chunk=0):
+    """Per-label AUC, AUPR and FDR of (N, L) scores against 0/1 targets
+    (evals.py:129-175) and their aggregates: ``{"allAUC", "allAUPR", "allFDR"}``
+    as (L,) fp64 device tensors (NaN where undefined) and the nine CURVE_KEYS
+    as 0-d fp64 device tensors (mean / median / population variance over the
+    labels that are not NaN; NaN when none is kept).  ``chunk`` is the number
+    of keys one workgroup sorts in LDS (0: the default; a smaller power of two
+    >= 64 forces the global merge passes at a small N -- the results do not
+    depend on it).  No host sync."""
+    H.require_gpu(predictions, targets)
+    p = predictions.detach().contiguous().float()
+    t = targets.detach().contiguous().float()
+    N, L = p.shape
+    lib = H.load_library()
+    nbytes = lib.mpv_curves_workspace_bytes(N, L, chunk)
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=p.device)
+    per = torch.empty((3, L), dtype=torch.float64, device=p.device)
+    agg = torch.empty(9, dtype=torch.float64, device=p.device)
+    a = H.CurveArgs(H.ptr(p), H.ptr(t), N, L, chunk, H.ptr(per[0]), H.ptr(per[1]), H.ptr(per[2]),
+                    H.ptr(agg))
+    H.check(lib.mpv_curve_metrics(ctypes.byref(a), H.ptr(ws), nbytes, H.stream_of(p.device)),
+            "mpv_curve_metrics")
+    res = {"allAUC": per[0], "allAUPR": per[1], "allFDR": per[2]}
+    res.update({k: agg[i] for i, k in enumerate(CURVE_KEYS)})
     return res
+
+
+def compute_metrics(predictions, targets, threshold, all_metrics=False, chunk=0):
+    """evals.compute_metrics (evals.py:178-238): the same keys, values 0-d fp64
+    device tensors.  all_metrics=False is the per-step call (the AUC / AUPR /
+    FDR entries 0 as in the reference); all_metrics=True adds ``curve_metrics``
+    (see there and the module docstring for ``chunk`` and the differences from
+    the reference).  No host sync either way."""
+    H.require_gpu(predictions, targets)
+    p = predictions.detach().contiguous().float()
+    t = targets.detach().contiguous().float()
+    out = _train_metrics(p, t, threshold)
+    res = {k: out[i] for i, k in enumerate(METRIC_KEYS)}
+    if all_metrics:
+        res.update(curve_metrics(p, t, chunk))
+    else:
+        for k in CURVE_KEYS + ["allAUC", "allAUPR", "allFDR"]:
+            res[k] = 0
+    return res
+
+
+def best_threshold_metrics(predictions, targets, thresholds=THRESHOLDS):
+    """The selection loop of validate_mpvae (fairsoft_train.py:400-416) on the
+    device: the METRICS of ``compute_metrics(..., thr, all_metrics=True)``
+    reduced over ``thresholds``, the maximum of each, the minimum for the FDR
+    entries.  The curve metrics (the FDR entries among them) do not depend on
+    the threshold, so they are computed once and are their own maximum and
+    minimum; the threshold metrics take one mpv_train_metrics call per
+    threshold and their maximum is reduced on the device.
+    Returns the 14 METRICS as 0-d fp64 device tensors; a NaN at any threshold
+    propagates (module docstring).  No host sync."""
+    H.require_gpu(predictions, targets)
+    p = predictions.detach().contiguous().float()
+    t = targets.detach().contiguous().float()
+    curves = curve_metrics(p, t)
+    per_thr = torch.stack([_train_metrics(p, t, thr) for thr in thresholds])  # (n_thr, 8)
+    best8 = per_thr.amax(0)  # propagates NaN; none of the eight is an FDR entry
+    best = {k: best8[i] for i, k in enumerate(METRIC_KEYS)}
+    return {k: best[k] if k in best else curves[k] for k in METRICS}

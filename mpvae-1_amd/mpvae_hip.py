@@ -13,7 +13,7 @@ import torch  # noqa: F401  (must precede the .so load: one HIP runtime per proc
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MPVAE_HIP_LIB", os.path.join(HERE, "libmpvae_hip.so"))
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 F32, F64 = 0, 1
 G_TOTAL, G_NLL, G_NLL_X, G_C, G_C_X, G_KL = range(6)
 
@@ -138,6 +138,12 @@ class FairArgs(ctypes.Structure):
                 ("out", vp)]
 
 
+class CurveArgs(ctypes.Structure):
+    """mpv_curve_args: validation AUC / AUPR / FDR over (N, L) scores (curves.hip)."""
+    _fields_ = [("pred", vp), ("target", vp), ("N", ctypes.c_int64), ("L", ctypes.c_int64),
+                ("chunk", ctypes.c_int64), ("auc", vp), ("aupr", vp), ("fdr", vp), ("agg", vp)]
+
+
 # name -> (restype, argtypes); exactly the symbols of include/mpvae_hip.h
 SIGNATURES = {
     "mpv_abi_version": (ctypes.c_int, []),
@@ -192,6 +198,9 @@ SIGNATURES = {
     "mpv_metrics_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64]),
     "mpv_train_metrics": (ctypes.c_int, [vp, vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_float,
                                          vp, vp, ctypes.c_size_t, vp]),
+    "mpv_curves_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64,
+                                                     ctypes.c_int64]),
+    "mpv_curve_metrics": (ctypes.c_int, [ctypes.POINTER(CurveArgs), vp, ctypes.c_size_t, vp]),
 }
 
 _lib = None
@@ -254,7 +263,7 @@ def require_gpu(*tensors):
 KERNELS = ["noise_philox", "split", "probit_fwd", "fwd_combine", "finalize", "bwd_coef", "bwd_elem",
            "dR_gemm", "sum_slabs", "convert", "bstat_combine", "reparam_fwd", "reparam_bwd",
            "kl_bwd", "label_weights", "fair_fwd", "fair_bwd", "metrics", "linear", "adam",
-           "adam_finish"]
+           "adam_finish", "curve_keys", "curve_sort", "curve_merge", "curve_pass", "curve_agg"]
 
 
 def kernel_times():
