@@ -26,18 +26,15 @@ constexpr float kKlWeight = 1.1f;
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// Probit probability of reference mpvae.py:171-180 (torch Normal.cdf) with the
-// ocml erf: E = 0.5 (1 + erf(u/sqrt2)) (1-1e-6) + 0.5e-6.  Reference-exact
-// formula, ~40 VALU ops with the piecewise erf; kept for A/B checks.
-MPV_DEV float probit_prob_erf(float u) {
-  float cdf = 0.5f * (1.0f + erff(u * kInvSqrt2));
-  return cdf * kC1 + kC0;
-}
-
 // Hardware transcendentals (v_exp_f32 / v_log_f32 are base 2).
-MPV_DEV float fast_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.4426950408889634f); }
 MPV_DEV float fast_log(float x) { return __builtin_amdgcn_logf(x) * 0.6931471805599453f; }
 MPV_DEV float fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
+
+// ---- packed fp32 (v_pk_fma/mul/add_f32: two lanes' worth per issue) -------
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+MPV_DEV f32x2 pk_fma(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
+MPV_DEV f32x2 splat2(float v) { return f32x2{v, v}; }
 
 // E of reference mpvae.py:171-180 with a branch-free erf: erfc(z), z = |u|/sqrt2,
 // from the Chebyshev fit of Numerical Recipes' erfcc, t exp(-z^2 + P(t)),
@@ -47,41 +44,10 @@ MPV_DEV float fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
 // the reference's order, so E carries the reference's own quantisation: near
 // saturation 1 + erf(x) rounds E to multiples of 2^-25, and the gradient's 1/E
 // and 1/(1-E) factors see the same E as the reference does.  Also returns the
-// normal density phi(u) = exp(-z^2)/sqrt(2 pi) for the backward.
-MPV_DEV float probit_eval(float u, float& phi) {
-  const float z = fabsf(u) * kInvSqrt2;
-  const float t = fast_rcp(fmaf(0.5f, z, 1.0f));
-  float p = fmaf(t, 0.17087277f, -0.82215223f);
-  p = fmaf(t, p, 1.48851587f);
-  p = fmaf(t, p, -1.13520398f);
-  p = fmaf(t, p, 0.27886807f);
-  p = fmaf(t, p, -0.18628806f);
-  p = fmaf(t, p, 0.09678418f);
-  p = fmaf(t, p, 0.37409196f);
-  p = fmaf(t, p, 1.00002368f);
-  p = fmaf(t, p, -1.26551223f);
-  const float ez = fast_exp(-z * z);
-  phi = ez * kInvSqrt2Pi;
-  const float erfc_z = t * ez * fast_exp(p);
-  const float erf_u = u < 0.0f ? __fsub_rn(erfc_z, 1.0f) : __fsub_rn(1.0f, erfc_z);
-  const float cdf = __fmul_rn(0.5f, __fadd_rn(1.0f, erf_u));
-  return __fadd_rn(__fmul_rn(cdf, kC1), kC0);
-}
-
-MPV_DEV float probit_prob(float u) {
-  float phi;
-  return probit_eval(u, phi);
-}
-
-// ---- packed fp32 (v_pk_fma/mul/add_f32: two lanes' worth per issue) -------
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-MPV_DEV f32x2 pk_fma(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
-MPV_DEV f32x2 splat2(float v) { return f32x2{v, v}; }
-
-// probit_eval of the label and feature branches at once (every step is the
-// same for both), bit-identical to two probit_eval calls: the fused steps are
-// explicit fmas and the reference-order steps stay separately rounded.
+// normal density phi(u) = exp(-z^2)/sqrt(2 pi).  The label (.x) and feature
+// (.y) branches go through together (every step is the same for both): the
+// fused steps are explicit fmas and the reference-order steps stay separately
+// rounded.  The fp32 forward's epilogue (fwd_tile_epilogue) uses it.
 MPV_DEV f32x2 probit_eval2(f32x2 u, f32x2& phi) {
 #pragma clang fp contract(off)
   const f32x2 z = f32x2{fabsf(u.x), fabsf(u.y)} * kInvSqrt2;
@@ -96,7 +62,7 @@ MPV_DEV f32x2 probit_eval2(f32x2 u, f32x2& phi) {
   p = pk_fma(t, p, splat2(0.37409196f));
   p = pk_fma(t, p, splat2(1.00002368f));
   p = pk_fma(t, p, splat2(-1.26551223f));
-  // fast_exp(x) = exp2(x * log2 e), as in probit_eval
+  // exp(x) = exp2(x * log2 e)
   const f32x2 az = (-z * z) * 1.4426950408889634f;
   const f32x2 ap = p * 1.4426950408889634f;
   const f32x2 ez = f32x2{__builtin_amdgcn_exp2f(az.x), __builtin_amdgcn_exp2f(az.y)};
@@ -108,46 +74,6 @@ MPV_DEV f32x2 probit_eval2(f32x2 u, f32x2& phi) {
   const f32x2 erf_u = f32x2{u.x < 0.0f ? -om.x : om.x, u.y < 0.0f ? -om.y : om.y};
   const f32x2 cdf = splat2(0.5f) * (splat2(1.0f) + erf_u);
   return cdf * kC1 + splat2(kC0);
-}
-
-// probit_eval2 on N independent pairs in lockstep (step-major): dependent
-// packed ops need a wait state between them, and N interleaved chains hide it.
-// Bit-identical to N probit_eval2 calls.
-template <int N>
-MPV_DEV void probit_eval2xN(const f32x2 (&u)[N], f32x2 (&E)[N], f32x2 (&phi)[N]) {
-#pragma clang fp contract(off)
-  f32x2 z[N], t[N], p[N];
-#pragma unroll
-  for (int j = 0; j < N; ++j) z[j] = f32x2{fabsf(u[j].x), fabsf(u[j].y)} * kInvSqrt2;
-#pragma unroll
-  for (int j = 0; j < N; ++j) {
-    const f32x2 den = pk_fma(splat2(0.5f), z[j], splat2(1.0f));
-    t[j] = f32x2{fast_rcp(den.x), fast_rcp(den.y)};
-  }
-  constexpr float c[10] = {0.17087277f, -0.82215223f, 1.48851587f, -1.13520398f, 0.27886807f,
-                           -0.18628806f, 0.09678418f, 0.37409196f, 1.00002368f, -1.26551223f};
-#pragma unroll
-  for (int j = 0; j < N; ++j) p[j] = pk_fma(t[j], splat2(c[0]), splat2(c[1]));
-#pragma unroll
-  for (int k = 2; k < 10; ++k)
-#pragma unroll
-    for (int j = 0; j < N; ++j) p[j] = pk_fma(t[j], p[j], splat2(c[k]));
-#pragma unroll
-  for (int j = 0; j < N; ++j) {
-    const f32x2 az = (-z[j] * z[j]) * 1.4426950408889634f;
-    const f32x2 ap = p[j] * 1.4426950408889634f;
-    const f32x2 ez = f32x2{__builtin_amdgcn_exp2f(az.x), __builtin_amdgcn_exp2f(az.y)};
-    const f32x2 ep = f32x2{__builtin_amdgcn_exp2f(ap.x), __builtin_amdgcn_exp2f(ap.y)};
-    phi[j] = ez * kInvSqrt2Pi;
-    z[j] = (t[j] * ez) * ep;  // erfc
-  }
-#pragma unroll
-  for (int j = 0; j < N; ++j) {
-    const f32x2 om = splat2(1.0f) - z[j];
-    const f32x2 erf_u = f32x2{u[j].x < 0.0f ? -om.x : om.x, u[j].y < 0.0f ? -om.y : om.y};
-    const f32x2 cdf = splat2(0.5f) * (splat2(1.0f) + erf_u);
-    E[j] = cdf * kC1 + splat2(kC0);
-  }
 }
 
 // Forward-only probit (no phi) on N pairs in lockstep: the erfcc form with a
@@ -180,9 +106,6 @@ constexpr float kPhiK = kC1 * kInvSqrt2Pi;  // dE/du = kPhiK exp(-u^2/2)
 // packed op fewer per element pair in the forward epilogue and the element
 // pass (forward -0.7 %, element pass -1.7 %, round 6), and the probit sweep's
 // per-band bounds unchanged (tests/test_gpu_probit_ulp.py)
-#ifndef MPV_OM_FMA
-#define MPV_OM_FMA 1
-#endif
 constexpr int kErfcDeg = 6;
 constexpr float kSqL2e = 1.2011224087864498f;  // sqrt(log2 e)
 constexpr float kZq = kInvSqrt2 * kSqL2e;
@@ -209,24 +132,10 @@ MPV_DEV void probit_w2xN_zq(const f32x2 (&zq)[N], f32x2 (&w)[N]) {
   for (int j = 0; j < N; ++j) {
     const f32x2 a = pk_fma(-zq[j], zq[j], p[j]);
     const f32x2 e = f32x2{__builtin_amdgcn_exp2f(a.x), __builtin_amdgcn_exp2f(a.y)};
-#if MPV_OM_FMA
     const f32x2 om = pk_fma(-t[j], e, splat2(1.0f));  // 1 - erfc, erfc = t e unrounded
-#else
-    const f32x2 om = splat2(1.0f) - t[j] * e;
-#endif
     w[j] = splat2(1.0f) +
            f32x2{__builtin_copysignf(om.x, zq[j].x), __builtin_copysignf(om.y, zq[j].y)};
   }
-}
-
-template <int N>
-MPV_DEV void probit_prob2xN(const f32x2 (&u)[N], f32x2 (&E)[N]) {
-  f32x2 zq[N];
-#pragma unroll
-  for (int j = 0; j < N; ++j) zq[j] = u[j] * kZq;
-  probit_w2xN_zq<N>(zq, E);
-#pragma unroll
-  for (int j = 0; j < N; ++j) E[j] = pk_fma(E[j], splat2(kEh), splat2(kC0));
 }
 
 // probit_w2xN_zq for the backward: w (E = kEh w + C0) and ez = exp(-u^2/2),
@@ -266,41 +175,9 @@ MPV_DEV void probit_dw2xN_zq(const f32x2 (&zq)[N], f32x2 (&w)[N], f32x2 (&ezo)[N
     const f32x2 az = -zq[j] * zq[j];
     const f32x2 ez = f32x2{__builtin_amdgcn_exp2f(az.x), __builtin_amdgcn_exp2f(az.y)};
     ezo[j] = ez;
-#if MPV_OM_FMA
     const f32x2 om = pk_fma(-(t[j] * ez), q[j], splat2(1.0f));
-#else
-    const f32x2 om = splat2(1.0f) - (t[j] * ez) * q[j];
-#endif
     w[j] = splat2(1.0f) +
            f32x2{__builtin_copysignf(om.x, zq[j].x), __builtin_copysignf(om.y, zq[j].y)};
-  }
-}
-
-// Scalar lockstep version (N independent evaluations, no packed ops):
-// bit-identical to N probit_eval calls (phi omitted).
-template <int N>
-MPV_DEV void probit_probN(const float (&u)[N], float (&E)[N]) {
-  float z[N], t[N], p[N];
-#pragma unroll
-  for (int j = 0; j < N; ++j) {
-    z[j] = fabsf(u[j]) * kInvSqrt2;
-    t[j] = fast_rcp(fmaf(0.5f, z[j], 1.0f));
-  }
-  constexpr float c[10] = {0.17087277f, -0.82215223f, 1.48851587f, -1.13520398f, 0.27886807f,
-                           -0.18628806f, 0.09678418f, 0.37409196f, 1.00002368f, -1.26551223f};
-#pragma unroll
-  for (int j = 0; j < N; ++j) p[j] = fmaf(t[j], c[0], c[1]);
-#pragma unroll
-  for (int k = 2; k < 10; ++k)
-#pragma unroll
-    for (int j = 0; j < N; ++j) p[j] = fmaf(t[j], p[j], c[k]);
-#pragma unroll
-  for (int j = 0; j < N; ++j) {
-    const float ez = fast_exp(-z[j] * z[j]);
-    const float erfc_z = t[j] * ez * fast_exp(p[j]);
-    const float erf_u = u[j] < 0.0f ? __fsub_rn(erfc_z, 1.0f) : __fsub_rn(1.0f, erfc_z);
-    const float cdf = __fmul_rn(0.5f, __fadd_rn(1.0f, erf_u));
-    E[j] = __fadd_rn(__fmul_rn(cdf, kC1), kC0);
   }
 }
 
@@ -336,17 +213,8 @@ MPV_DEV void row16_sum_to_lane15_n(float (&v)[N]) {
 
 // Sum over the four 16-lane rows of the wave (lanes l, l^16, l^32, l^48) by
 // the gfx950 row-swap permutes (VALU, no LDS): every lane gets the total.
-MPV_DEV float sum_lanegroups(float v) {
-  const auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false,
-                                                  false);
-  v = __uint_as_float(a[0]) + __uint_as_float(a[1]);
-  const auto c = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false,
-                                                  false);
-  return __uint_as_float(c[0]) + __uint_as_float(c[1]);
-}
-
-// sum_lanegroups of N values step-major (independent chains between the
-// permutes instead of wait states).
+// N values step-major (independent chains between the permutes instead of
+// wait states).
 template <int N>
 MPV_DEV void sum_lanegroups_n(float (&v)[N]) {
 #pragma unroll

@@ -39,10 +39,7 @@ constexpr float kBoundDl = 4.5f, kBoundPos = 0.4f, kBoundNeg = 60.0f, kBoundInd 
 // --------------------------------------------------------------- coefficients
 // bwd_coef: one workgroup per batch row of 512 threads (1024: C2 +1.3 us, C3
 // +-0, round 6; 256: C2 +1.7, C3 +2, C4 +3 us against 512, round 3)
-#ifndef MPV_COEF_THREADS
-#define MPV_COEF_THREADS 512
-#endif
-constexpr int kCoefThreads = MPV_COEF_THREADS;
+constexpr int kCoefThreads = 512;
 
 __global__ __launch_bounds__(kCoefThreads) void bwd_coef_kernel(
     const float* __restrict__ y, const float* __restrict__ rowstat, const float* __restrict__ bstat,
@@ -254,7 +251,6 @@ struct ElemRow {
   float t[4];
 };
 
-template <bool VEC>
 MPV_DEV void elem_row_load(ElemRow& r, const ElemParams& p, int b, int s, int c0,
                            const bool (&ok)[4]) {
   const int64_t cb = (int64_t)b * p.S + s;
@@ -263,7 +259,7 @@ MPV_DEV void elem_row_load(ElemRow& r, const ElemParams& p, int b, int s, int c0
   r.bP = f32x2{p.coef[1 * BS + cb], p.coef[4 * BS + cb]};
   r.bN = f32x2{p.coef[2 * BS + cb], p.coef[5 * BS + cb]};
   const float* row = p.T + cb * p.ldT;
-  if (VEC && c0 < p.L) {  // t_cols rows: the pad columns are readable
+  if (c0 < p.L) {  // t_cols rows: the pad columns are readable
     // nontemporal T loads and G-plane stores: element pass -5 %
     const f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(row + c0));
     r.t[0] = v[0]; r.t[1] = v[1]; r.t[2] = v[2]; r.t[3] = v[3];
@@ -304,29 +300,20 @@ MPV_DEV void elem_col_setup(const ElemParams& p, int b, int c0, bool active, boo
   }
 }
 
-// Rows of T in flight per thread beyond the one computing (kElemLookahead),
-// and ONE: a block row covers all its columns (RPI == 1), so the row index and
-// the six per-row coefficients are wave-uniform (scalar loads, no VGPRs).
-// Otherwise (L < 1024: C2, C3) they are per-lane, 12 more VGPRs than fit in
-// 128: those instantiations run at 3 waves per SIMD instead of spilling.
-#ifndef MPV_ELEM_LA
-#define MPV_ELEM_LA 1
-#endif
-constexpr int kElemLookahead = MPV_ELEM_LA;  // 2, 3: C3 element pass 0.111 -> 0.120 ms (r06_la_ab.json)
-#ifndef MPV_ELEM_MIN_ROWS
-#define MPV_ELEM_MIN_ROWS 16
-#endif
-constexpr int kElemMinRows = MPV_ELEM_MIN_ROWS;  // minimum T rows per thread (C2 -6 %)
-#ifndef MPV_ELEM_OCC4
-#define MPV_ELEM_OCC4 0  // 4 waves per SIMD for per-lane rows too: slower (r06_elem_occ4_ab.json)
-#endif
-template <bool VEC, bool PLANES, bool ONE>
-__global__ __launch_bounds__(256, (ONE || MPV_ELEM_OCC4) ? 4 : 3) void bwd_elem_kernel(ElemParams p) {
+// Rows of T in flight per thread beyond the one computing (kElemLookahead).
+// The row index and the six per-row coefficients are per-lane (a block row
+// holds RPI rows of TPR threads), 12 more VGPRs than fit in 128: the kernel
+// runs at 3 waves per SIMD instead of spilling (4 waves per SIMD: slower,
+// profiles/r06_elem_occ4_ab.json).
+constexpr int kElemLookahead = 1;  // 2, 3: C3 element pass 0.111 -> 0.120 ms (r06_la_ab.json)
+constexpr int kElemMinRows = 16;   // minimum T rows per thread (C2 -6 %)
+template <bool PLANES>
+__global__ __launch_bounds__(256, 3) void bwd_elem_kernel(ElemParams p) {
   constexpr int LA = kElemLookahead;
   __shared__ float cred[256 * 8];
   const int b = blockIdx.x, sc = blockIdx.y;
   const int tid = threadIdx.x;
-  const int rsub = ONE ? 0 : tid / p.TPR, cq = ONE ? tid : tid % p.TPR;
+  const int rsub = tid / p.TPR, cq = tid % p.TPR;
   const bool active = rsub < p.RPI;
   const int c0 = blockIdx.z * 1024 + cq * 4;
   const int S = p.S, B = p.B, L = p.L;
@@ -341,13 +328,13 @@ __global__ __launch_bounds__(256, (ONE || MPV_ELEM_OCC4) ? 4 : 3) void bwd_elem_
   if (active && c0 < p.Lc) {
     // LA rows of lookahead: rows s+RPI .. s+LA*RPI are in flight while row s
     // computes (the element math and the T stream overlap)
-    const int s0 = s_begin + rsub, R = ONE ? 1 : p.RPI;
+    const int s0 = s_begin + rsub, R = p.RPI;
     ElemRow buf[LA + 1];
 #pragma unroll
     for (int j = 0; j < LA; ++j)
-      if (s0 + j * R < s_end) elem_row_load<VEC>(buf[j], p, b, s0 + j * R, c0, ok);
+      if (s0 + j * R < s_end) elem_row_load(buf[j], p, b, s0 + j * R, c0, ok);
     for (int s = s0; s < s_end; s += R) {
-      if (s + LA * R < s_end) elem_row_load<VEC>(buf[LA], p, b, s + LA * R, c0, ok);
+      if (s + LA * R < s_end) elem_row_load(buf[LA], p, b, s + LA * R, c0, ok);
       const ElemRow& cur = buf[0];
       const int64_t cb = (int64_t)b * S + s;
       float G[4];
@@ -375,7 +362,7 @@ __global__ __launch_bounds__(256, (ONE || MPV_ELEM_OCC4) ? 4 : 3) void bwd_elem_
         __builtin_nontemporal_store(lv, reinterpret_cast<s16x4*>(p.g + o + kLoOff));
       } else {
         float* row = p.T + cb * p.ldT;
-        if (VEC && c0 < L) {  // pad columns get G = 0
+        if (c0 < L) {  // pad columns get G = 0
           *reinterpret_cast<f32x4*>(row + c0) = f32x4{G[0], G[1], G[2], G[3]};
         } else {
 #pragma unroll
@@ -426,9 +413,6 @@ __global__ __launch_bounds__(256, (ONE || MPV_ELEM_OCC4) ? 4 : 3) void bwd_elem_
 constexpr int kElemRing = 8;       // T rows in flight per wave (1 KB each; 8: 3 waves per SIMD)
 constexpr int kElemRingRows = 256;  // rows per sub-chunk (the coefficient copy)
 constexpr int kElemRingMinRows = 128;  // rows per block at least (plan_bwd; 64: +0.3 % at S 512)
-#ifndef MPV_ELEM_SEL
-#define MPV_ELEM_SEL 1  // per-lane ranking-coefficient addresses, scalar-base stores
-#endif
 // The rows of one sub-chunk [sb, sb + nrows) for one wave; SOFT: the block
 // holds soft labels (block-uniform, so either loop is one basic block).
 // MASK: some lane of the wave has columns past L or past the planes (their G is
@@ -454,7 +438,6 @@ MPV_DEV void elem_ring_rows(const ElemParams& p, const ElemCol& ec, const bool (
   };
   const int pro = min(NR, nrows);
   for (int r = 0; r < pro; ++r) issue(r);
-#if MPV_ELEM_SEL
   // each column's ranking coefficient read from its own cf address (rkp at
   // byte 0 of a row, rkn at 16; alpha at 8 and 24, so 8 past either): no
   // per-row select
@@ -465,12 +448,10 @@ MPV_DEV void elem_ring_rows(const ElemParams& p, const ElemCol& ec, const bool (
   const uint32_t loffb = live ? 2u * (uint32_t)(((c0 >> 5) << 6) + (c0 & 31)) : 0u;
   f32x2 qc1 = splat2(kErfcxC1);
   asm volatile("" : "+v"(qc1));
-#endif
   auto row = [&](int r) {
     const f32x4 tv = *reinterpret_cast<const f32x4*>(myring + (r % NR) * 256 + lane * 4);
     const float t[4] = {tv[0], tv[1], tv[2], tv[3]};
     f32x2 g2[4];
-#if MPV_ELEM_SEL
     // (the row offset opaque: a scalar, so each address is one add)
     const char* crow =
         reinterpret_cast<const char*>(&cf[0][0]) + __builtin_amdgcn_readfirstlane(r * 32);
@@ -486,12 +467,6 @@ MPV_DEV void elem_ring_rows(const ElemParams& p, const ElemCol& ec, const bool (
       const f32x2 alpha = *reinterpret_cast<const f32x2*>(crow + rsel[0] + 8);
       d_elem2x4<SOFT, false, true>(t, ec, alpha, rkp, rkn, g2, rkq, &qc1);
     }
-#else
-    const f32x4 ca = *reinterpret_cast<const f32x4*>(&cf[r][0]);
-    const f32x2 rkn = *reinterpret_cast<const f32x2*>(&cf[r][4]);
-    const f32x2 alpha = f32x2{ca[0], ca[1]}, rkp = f32x2{ca[2], ca[3]};
-    d_elem2x4<SOFT, false, true>(t, ec, alpha, rkp, rkn, g2);
-#endif
     // a degenerate row poisons every label (the row's rkp is wave-uniform)
     if (NANCHK && __builtin_amdgcn_readfirstlane((rkp.x != rkp.x || rkp.y != rkp.y) ? 1 : 0)) {
 #pragma unroll
@@ -510,7 +485,6 @@ MPV_DEV void elem_ring_rows(const ElemParams& p, const ElemCol& ec, const bool (
     uint32_t hv[2], lv[2];
     split2_f16(G[0], G[1], gs, hv[0], lv[0]);
     split2_f16(G[2], G[3], gs, hv[1], lv[1]);
-#if MPV_ELEM_SEL
     // the row base made opaque so it stays a scalar base (saddr stores with a
     // 32-bit lane offset, no 64-bit address add per row)
     const uint64_t ga = reinterpret_cast<uint64_t>(p.g + (rowb + r) * p.gld);
@@ -527,13 +501,6 @@ MPV_DEV void elem_ring_rows(const ElemParams& p, const ElemCol& ec, const bool (
                    : "v"(loffb), "v"(u32x2{hv[0], hv[1]}), "s"(grow), "v"(u32x2{lv[0], lv[1]}),
                      "i"(2 * kLoOff));
     }
-#else
-    const int64_t o = chunked_index(rowb + r, p.gld, live ? c0 : 0);
-    if (!MASK || live) {  // nontemporal plane stores (the element pass -2 %, round 2)
-      __builtin_nontemporal_store(u32x2{hv[0], hv[1]}, reinterpret_cast<u32x2*>(p.g + o));
-      __builtin_nontemporal_store(u32x2{lv[0], lv[1]}, reinterpret_cast<u32x2*>(p.g + o + kLoOff));
-    }
-#endif
     if (r + NR < nrows) issue(r + NR);  // into the slot row r was just read from
   };
   // Before row r is read, the ops issued after its DMA are the DMAs of rows
@@ -562,7 +529,7 @@ MPV_DEV void elem_ring_rows(const ElemParams& p, const ElemCol& ec, const bool (
 __global__ __launch_bounds__(256, 3) void bwd_elem_ring_kernel(ElemParams p) {
   constexpr int NR = kElemRing, CR = kElemRingRows;
   __shared__ __attribute__((aligned(16))) float ring[4][NR][256];  // [wave][slot][1 KB]
-  __shared__ __attribute__((aligned(16))) float cf[CR][8];  // alpha, bP, bN (label, feature)
+  __shared__ __attribute__((aligned(16))) float cf[CR][8];  // rkp, alpha, rkn, alpha (label, feature)
   const int b = blockIdx.x, sc = blockIdx.y, tid = threadIdx.x;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int c0 = blockIdx.z * 1024 + tid * 4;
@@ -592,7 +559,8 @@ __global__ __launch_bounds__(256, 3) void bwd_elem_ring_kernel(ElemParams p) {
   for (int sb = s_begin; sb < s_end; sb += CR) {  // sub-chunks of <= CR rows
     const int nrows = min(CR, s_end - sb);
     __syncthreads();  // the previous sub-chunk's cf reads are done
-    // coef is [k][b][s]: cf[row] = alpha, rkp, rkn as (label, feature) pairs
+    // coef is [k][b][s]: cf[row] = rkp, alpha, rkn, alpha as (label, feature)
+    // pairs (alpha 8 bytes past either ranking coefficient: elem_ring_rows)
     bool nan_row = false;
     for (int r = tid; r < nrows; r += 256) {
       const int64_t o = (int64_t)b * S + sb + r;
@@ -602,13 +570,8 @@ __global__ __launch_bounds__(256, 3) void bwd_elem_ring_kernel(ElemParams p) {
       f32x2 rkp, rkn;
       elem_rank_coefs(ec, bP, bN, rkp, rkn);
       nan_row |= bP.x != bP.x || bP.y != bP.y;
-#if MPV_ELEM_SEL
       *reinterpret_cast<f32x4*>(&cf[r][0]) = f32x4{rkp.x, rkp.y, alpha.x, alpha.y};
       *reinterpret_cast<f32x4*>(&cf[r][4]) = f32x4{rkn.x, rkn.y, alpha.x, alpha.y};
-#else
-      *reinterpret_cast<f32x4*>(&cf[r][0]) = f32x4{alpha.x, alpha.y, rkp.x, rkp.y};
-      *reinterpret_cast<f32x2*>(&cf[r][4]) = rkn;
-#endif
     }
     const bool nan_any = __syncthreads_or(nan_row) != 0;
     if (!wave_live) continue;
@@ -853,7 +816,7 @@ MPV_DEV void dr_read(DrFrag<TM, TN>& f, const char* base, int wm, int wn, int r0
 // dr_read with a group-0 wave's share of the next stage's LDS-DMA woven in:
 // one or two 1-KB pieces after each tile's four transposed reads, so the
 // CU's load path (the DMA) and the LDS (the reads) work side by side instead
-// of the reads queueing behind the whole DMA burst (tools/studies/dr_stamps.py: DMA
+// of the reads queueing behind the whole DMA burst (profiles/r05_dr_ab.json: DMA
 // issue 1060 + reads 960 ticks, serial, against 1650 for the other group's
 // MFMAs).  Noise rows past the last real one (a padded last stage) repeat
 // that row, as drs_issue_range clamps them.
@@ -934,29 +897,6 @@ MPV_DEV void drs_issue_range(const Dr16Params& p, char* dst, int q0, int rows, i
   }
 }
 
-// Timing study (MPV_DR_STAMPS=1 builds only, tools/studies/dr_stamps.py): s_memtime
-// at the slot boundaries of workgroup 0's waves over its first kDrStampStages
-// stages, stored by lane 0 with vector stores; read back through
-// mpv_study_dr_stamps.
-#ifndef MPV_DR_STAMPS
-#define MPV_DR_STAMPS 0
-#endif
-[[maybe_unused]] constexpr int kDrStampStages = 64, kDrStampPts = 6;
-#if MPV_DR_STAMPS
-__device__ unsigned long long mpv_dr_stamps[8][kDrStampStages][kDrStampPts];
-#define DR_STAMP(i, k)                                                                           \
-  do {                                                                                           \
-    if (blockIdx.x == 0 && (i) < kDrStampStages) {                                               \
-      const unsigned long long t_ = __builtin_amdgcn_s_memtime();                                \
-      if (lane == 0) mpv_dr_stamps[wid][(i)][(k)] = t_;                                         \
-    }                                                                                            \
-  } while (0)
-#else
-#define DR_STAMP(i, k) \
-  do {                 \
-  } while (0)
-#endif
-
 // A group-0 wave's share of every stage's LDS-DMA: PER_WAVE consecutive rows
 // of one operand (the first WN/2 waves G rows, the others noise rows), walked
 // by 64-bit pointer increments -- two SALU per row instead of the ~14 of a
@@ -997,7 +937,7 @@ struct DrsDma {
 //   mma(i): 96 MFMAs; group 0 then waits for its stage i+1 DMA, so stage i+1
 //           is visible to both groups after the slot's barrier.
 // Two 64-KB stage images; DMA latency budget = one slot pair.  Round 5
-// (tools/studies/dr_stamps.py, profiles/r05_dr_ab.json): with the DMA as a burst ahead
+// (the slot-timing study in profiles/r05_dr_ab.json): with the DMA as a burst ahead
 // of the reads, group 0's mem slot (1060 + 960 ticks) outlasted the other
 // group's MFMAs (1650) every slot; woven, dR -4.2 %.  Measured slower: group 1
 // issuing the stream between its own MFMAs (+2.3 %), half of it in each
@@ -1057,20 +997,15 @@ __global__ __launch_bounds__(WM* WN * 64, 1) void dR16s_kernel(Dr16Params p) {
     // of stage i, then stage i+1 landed before the closing barrier
     int i = 0;
     for (; i + 1 < nst; ++i) {
-      DR_STAMP(i, 0);
       dr_read_dma<TM, TN, ROWB, IMG, PER_WAVE>(f, smem + (i & 1) * STAGE, wm, wn, r0, r1, sw, tp,
                                                dma, smem + (1 - (i & 1)) * STAGE, rows, lane_u,
                                                lane_h);
       lds_barrier();
-      DR_STAMP(i, 2);
       __builtin_amdgcn_s_setprio(1);
       dr_mfma<TM, TN>(acc, f);
       __builtin_amdgcn_s_setprio(0);
-      DR_STAMP(i, 3);
       wait_vmcnt<0>();
-      DR_STAMP(i, 4);
       barrier_raw();
-      DR_STAMP(i, 5);
     }
     for (; i < nst; ++i) {  // the last stage: nothing to stream
       dr_read<TM, TN, ROWB, IMG>(f, smem + (i & 1) * STAGE, wm, wn, r0, r1, sw, tp);
@@ -1085,16 +1020,12 @@ __global__ __launch_bounds__(WM* WN * 64, 1) void dR16s_kernel(Dr16Params p) {
     barrier_raw();
     // slot 2i+1: read stage i; slot 2i+2: MFMAs of stage i
     for (int i = 0; i < nst; ++i) {
-      DR_STAMP(i, 0);
       dr_read<TM, TN, ROWB, IMG>(f, smem + (i & 1) * STAGE, wm, wn, r0, r1, sw, tp);
       lds_barrier();
-      DR_STAMP(i, 2);
       __builtin_amdgcn_s_setprio(1);
       dr_mfma<TM, TN>(acc, f);
       __builtin_amdgcn_s_setprio(0);
-      DR_STAMP(i, 3);
       barrier_raw();
-      DR_STAMP(i, 5);
     }
   }
   const float inv = 1.0f / (wave_pow2_scale(p.g_bound, p.B) * *p.eps16.scale);
@@ -1460,13 +1391,13 @@ int mpv_probit_bwd(const mpv_shape* shape, const mpv_bwd_args* a, void* stream) 
   ep.rows_per_chunk = pl.rows_per_chunk;
   ep.inv_S = 1.0f / (float)shape->S_total;
   const dim3 eg(B, pl.nSc, pl.nLc);
-  // t_cols rows: 16-B aligned, whole float4 reads (VEC)
+  // t_cols rows: 16-B aligned, whole float4 reads
   if (want_planes && pl.RPI == 1)  // L >= 1024: the LDS-ring element pass
     MPV_LAUNCH("bwd_elem", bwd_elem_ring_kernel, eg, dim3(256), 0, st, ep);
   else if (want_planes)
-    MPV_LAUNCH("bwd_elem", (bwd_elem_kernel<true, true, false>), eg, dim3(256), 0, st, ep);
+    MPV_LAUNCH("bwd_elem", bwd_elem_kernel<true>, eg, dim3(256), 0, st, ep);
   else
-    MPV_LAUNCH("bwd_elem", (bwd_elem_kernel<true, false, false>), eg, dim3(256), 0, st, ep);
+    MPV_LAUNCH("bwd_elem", bwd_elem_kernel<false>, eg, dim3(256), 0, st, ep);
   if (int rc = check_launch("bwd_elem")) return rc;
   if (!dR_out) {
     if (int rc = launch_sum_slabs(colpart, pl.nSc, 2 * (int64_t)B * L, a->dfe_dfx, MPV_F32, st))
@@ -1525,11 +1456,4 @@ int mpv_probit_bwd(const mpv_shape* shape, const mpv_bwd_args* a, void* stream) 
   return MPV_OK;
 }
 
-#if MPV_DR_STAMPS
-// study builds only: copy workgroup 0's slot stamps (8 x 64 x 6 u64) to host
-int mpv_study_dr_stamps(unsigned long long* host) {
-  return hipMemcpyFromSymbol(host, HIP_SYMBOL(mpv_dr_stamps), sizeof(mpv_dr_stamps), 0,
-                             hipMemcpyDeviceToHost) == hipSuccess ? 0 : 1;
-}
-#endif
 }  // extern "C"

@@ -1,13 +1,23 @@
 // Forward of the MPVAE probit ELBO for one S-shard (reference mpvae.py:145-210).
 //
-//   probit_fwd16_kernel  t = eps . R^T with 3xf16 split operands on the f16
-//                        matrix cores (v_mfma_f32_16x16x32_f16, fp32 accumulate,
-//                        ~fp32 accuracy, see mpv_common.h), operand tiles
-//                        streamed global->LDS by LDS-DMA (global_load_lds_dwordx4)
-//                        into a double-buffered, XOR-swizzled image.
-//   probit_fwd_kernel    the same with exact fp32 MFMA (v_mfma_f32_16x16x4_f32)
-//                        on fp32 operands (MPV_GEMM_F32, the bit-faithful mode).
-//   Both share the fused epilogue: u = t + fe_out / fx_out,
+// t = eps . R^T with 3xf16 split operands on the f16 matrix cores
+// (v_mfma_f32_16x16x32_f16, fp32 accumulate, ~fp32 accuracy, see mpv_common.h),
+// operand tiles streamed global->LDS by LDS-DMA (global_load_lds_dwordx4) into
+// a double-buffered, XOR-swizzled image; accumulators transposed (MFMA-M =
+// labels).  Every 3xf16 tile is 8 waves, one workgroup per CU (launch_fwd):
+//   probit_fwd16t_kernel  even sample split: 48 labels x 256 samples (L <= 48)
+//                         and 96 labels x 128 samples (48 < L <= 96).
+//   probit_fwd16a_kernel  asymmetric 80 / 48 sample split: 128 labels x 128
+//                         samples (96 < L <= 128), and 256 labels x 128 samples
+//                         (L > 128 with S < 256, or MPVAE_FWD_TILE=256x128).
+//   probit_fwd16b_kernel  256 labels x 256 samples (L > 128 and S >= 256: the
+//                         C4 / C5 tile).
+//   probit_fwd_kernel     the same product with exact fp32 MFMA
+//                         (v_mfma_f32_16x16x4_f32) on fp32 operands
+//                         (MPV_GEMM_F32, the bit-faithful mode): 48, 96 or 128
+//                         labels x 128 samples, MFMA-layout accumulators.
+//   All share the fused epilogue's arithmetic (fwd_tile_epilogue_t for the
+//   transposed tiles, fwd_tile_epilogue for fp32): u = t + fe_out / fx_out,
 //   E = Phi(u)(1-1e-6)+0.5e-6 for both branches, per-row BCE log-prob and
 //   ranking factors P, N (partial over this label tile), column sums of E over
 //   s, optional T stash for the backward.
@@ -52,10 +62,7 @@ struct FwdParams {
 // lists the variants that lost and were removed):
 // fwd_combine: one block per batch row (512 / 256 threads: C4 0.076 -> 0.115 /
 // 0.188 ms, C3 0.023 -> 0.027 / 0.038 ms; round 3; 512 at C2 / C3 +-0, round 6)
-#ifndef MPV_COMBINE_THREADS
-#define MPV_COMBINE_THREADS 1024
-#endif
-constexpr int kCombineThreads = MPV_COMBINE_THREADS;
+constexpr int kCombineThreads = 1024;
 constexpr int kCombineFoldSlabs = 64;  // s-chunk partials fwd_combine sums itself, at most
 constexpr int kCombineKeep = 4;        // fwd_combine: samples per thread kept in registers
 constexpr int kFwdWant = 2048;         // fp32 mode: target workgroup count of the forward grid
@@ -71,31 +78,12 @@ constexpr int kFwd48BM = 256;
 //             11 and 12 spill
 //   kFwdBPart sample blocks per epilogue part: 1 -> 13.44, 2 -> 12.79
 //   kFwdBCQ   column-sum slots per 16-lane row: 4 (lane quads) -> 12.58
-//   kFwdBEpi, kFwdBUnroll: the label loop's scheduling knobs (fwd_tile_epilogue_t)
-#ifndef MPV_FWD_B
-#define MPV_FWD_B 1
-#endif
-#ifndef MPV_FWD_BA
-#define MPV_FWD_BA 10
-#endif
-#ifndef MPV_FWD_BPART
-#define MPV_FWD_BPART 2
-#endif
-#ifndef MPV_FWD_BCQ
-#define MPV_FWD_BCQ 4
-#endif
-#ifndef MPV_FWD_BEPI
-#define MPV_FWD_BEPI 2
-#endif
-#ifndef MPV_FWD_BUNROLL
-#define MPV_FWD_BUNROLL 0
-#endif
-constexpr bool kFwdB = MPV_FWD_B;
-constexpr int kFwdBA = MPV_FWD_BA;
-constexpr int kFwdBPart = MPV_FWD_BPART;
-constexpr int kFwdBCQ = MPV_FWD_BCQ;
-constexpr int kFwdBEpi = MPV_FWD_BEPI;
-constexpr bool kFwdBUnroll = MPV_FWD_BUNROLL;
+//   kFwdBEpi  sample blocks between the label loop's scheduling barriers
+//             (fwd_tile_epilogue_t's EPI_BLOCKS)
+constexpr int kFwdBA = 10;
+constexpr int kFwdBPart = 2;
+constexpr int kFwdBCQ = 4;
+constexpr int kFwdBEpi = 2;
 
 constexpr int kBK = 32;   // fp32 mode: K (= z) chunk staged in LDS
 constexpr int kLDK = 40;  // fp32 mode: LDS row stride in floats (conflict-free ds_read_b128)
@@ -152,36 +140,6 @@ MPV_DEV void fwd_cols_load(FwdCols<TN>& c, const FwdParams& p, int b, int n0, in
   }
 }
 
-// The same from an LDS copy cols[3][BN] (fe, fx, y of the workgroup's label
-// tile, staged once by fwd_cols_stage), so nothing is held in registers or
-// re-fetched from global memory across tiles.
-template <int WN, int TN>
-MPV_DEV void fwd_cols_lds(FwdCols<TN>& c, const float* cols, int L, int n0, int wn, int lr) {
-  constexpr int BN = WN * TN * 16;
-#pragma unroll
-  for (int n = 0; n < TN; ++n) {
-    const int cl = wn * TN * 16 + n * 16 + lr;
-    c.col[n] = n0 + cl;
-    c.colok[n] = n0 + cl < L;
-    c.fe[n] = cols[cl];
-    c.fx[n] = cols[BN + cl];
-    c.y[n] = cols[2 * BN + cl];
-    c.soft[n] = !(c.y[n] == 0.0f || c.y[n] == 1.0f);
-  }
-}
-
-template <int BN>
-MPV_DEV void fwd_cols_stage(float* cols, const FwdParams& p, int b, int n0, int nthreads) {
-  for (int i = threadIdx.x; i < BN; i += nthreads) {
-    const int col = n0 + i;
-    const bool ok = col < p.L;
-    const int64_t o = (int64_t)b * p.L + (ok ? col : 0);
-    cols[i] = ok ? p.fe[o] : 0.0f;
-    cols[BN + i] = ok ? p.fx[o] : 0.0f;
-    cols[2 * BN + i] = ok ? p.y[o] : 0.0f;
-  }
-}
-
 // The transposed kernel's layout (kColsT * BN floats): (fe, fx) pairs, then
 // y[BN], then the epilogue's per-label constants, one BN array each (so a
 // lane reads its 4 labels' values as one f32x4): qa, qb (q = qa E + qb: E for
@@ -218,22 +176,13 @@ MPV_DEV void fwd_cols_stage_t(float* cols, const FwdParams& p, int b, int n0, in
 // every thread of the workgroup; uses `smem` (>= WN*BM*6 floats).
 template <int WM, int WN, int TM, int TN>
 MPV_DEV void fwd_tile_epilogue(const FwdParams& p, FwdLane<TN>& ln, f32x4 (&acc)[TM][TN],
-                               float scale, int b, int s0, int s_own, int nt, float* smem,
-                               const float* cols = nullptr) {
+                               float scale, int b, int s0, int s_own, int nt, float* smem) {
   constexpr int NT = WM * WN * 64, BM = WM * TM * 16, BN = WN * TN * 16;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wm = wid / WN, wn = wid % WN, lr = lane & 15, lg = lane >> 4;
-  const int S = p.S, B = p.B, L = p.L;
+  const int S = p.S, B = p.B;
   FwdCols<TN> cl;
-  if (cols != nullptr) {
-    // opaque per call: keeps the column constants (and everything derived
-    // from them) from being hoisted out of the tile loop into registers that
-    // would then live across the main loop
-    int zero = 0;
-    asm volatile("" : "+s"(zero));
-    fwd_cols_lds<WN, TN>(cl, cols + zero, L, nt * BN + zero, wn, lr);
-  } else
-    fwd_cols_load<WN, TN>(cl, p, b, nt * BN, wn, lr);
+  fwd_cols_load<WN, TN>(cl, p, b, nt * BN, wn, lr);
   float* red = smem;  // [WN][BM][6]
   lds_barrier();      // the main loop's last LDS reads are done before red is written
 #pragma unroll
@@ -576,115 +525,6 @@ struct Fwd16Dma {
   }
 };
 
-// Operand fragments of one K stage: A (eps rows) and B (R rows), hi and lo.
-template <int TM, int TN>
-struct Frag16 {
-  s16x8 ah[TM], al[TM], bh[TN], bl[TN];
-};
-
-// coh / col: swizzled byte positions of this lane's hi and lo units
-template <int TM, int TN, int BM>
-MPV_DEV void fwd16_read(Frag16<TM, TN>& f, const char* base, int wm, int wn, int lr, int coh,
-                        int col) {
-#pragma unroll
-  for (int m = 0; m < TM; ++m) {
-    const int off = ((wm * TM + m) * 16 + lr) * kRowB;
-    f.ah[m] = *reinterpret_cast<const s16x8*>(base + off + coh);
-    f.al[m] = *reinterpret_cast<const s16x8*>(base + off + col);
-  }
-#pragma unroll
-  for (int n = 0; n < TN; ++n) {
-    const int off = (BM + (wn * TN + n) * 16 + lr) * kRowB;
-    f.bh[n] = *reinterpret_cast<const s16x8*>(base + off + coh);
-    f.bl[n] = *reinterpret_cast<const s16x8*>(base + off + col);
-  }
-}
-
-// acc += hi*hi + hi*lo + lo*hi for one K stage.
-template <int TM, int TN>
-MPV_DEV void fwd16_mfma(f32x4 (&acc)[TM][TN], const Frag16<TM, TN>& f) {
-#pragma unroll
-  for (int m = 0; m < TM; ++m)
-#pragma unroll
-    for (int n = 0; n < TN; ++n) {
-      acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(as_f16x8(f.ah[m]), as_f16x8(f.bh[n]),
-                                                         acc[m][n], 0, 0, 0);
-      acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(as_f16x8(f.ah[m]), as_f16x8(f.bl[n]),
-                                                         acc[m][n], 0, 0, 0);
-      acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(as_f16x8(f.al[m]), as_f16x8(f.bh[n]),
-                                                         acc[m][n], 0, 0, 0);
-    }
-}
-
-// Main loop: a ring of NSTAGE stage images, NSTAGE-1 stages in flight, one
-// raw barrier per stage (the DMA stream runs across tile seams).
-// Two 4-wave workgroups share each CU (the 48-label tile, 70 KB of LDS):
-// no packed fp32 (MPV_NO_PK_FP32, above).
-template <int WM, int WN, int TM, int TN, int NSTAGE>
-__global__ MPV_NO_PK_FP32 __launch_bounds__(WM* WN * 64, (WM * WN <= 4) ? 2 : 1) void probit_fwd16_kernel(FwdParams p) {
-  constexpr int NW = WM * WN;
-  constexpr int BM = WM * TM * 16, BN = WN * TN * 16;
-  constexpr int STAGE = (BM + BN) * kRowB;
-  static_assert(BM % 8 == 0 && BN % 8 == 0, "operand images are whole 8-row DMA pieces");
-  constexpr int RED = (WN * BM * 6 > WM * BN * 2 ? WN * BM * 6 : WM * BN * 2) * 4;
-  // one __shared__ array: stage ring, the epilogue's reduction area, and the
-  // label tile's fe/fx/y
-  __shared__ __attribute__((aligned(1024))) char smem[NSTAGE * STAGE + RED + 3 * BN * 4];
-  float* red = reinterpret_cast<float*>(smem + NSTAGE * STAGE);
-  float* cols = reinterpret_cast<float*>(smem + NSTAGE * STAGE + RED);
-
-  int g, nt;
-  decode_block(blockIdx.x, p.B * p.nSc, p.nNt, g, nt);
-  const int b = g / p.nSc, sc = g % p.nSc;
-  const int n0 = nt * BN;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wid / WN, wn = wid % WN;
-  const int lr = lane & 15, lg = lane >> 4;
-
-  FwdLane<TN> ln;
-  fwd_lane_init<WN, TN>(ln);
-  const float scale = 1.0f / (*p.eps16.scale * *p.R16.scale);
-  const int nK = (p.z + kKC - 1) / kKC;
-  const int sw = (lr >> 1) & 7;
-  const int coh = (lg ^ sw) << 4, col = ((4 + lg) ^ sw) << 4;
-  const int t_begin = sc * p.tps, t_end = min(p.nSt, (sc + 1) * p.tps);
-
-  fwd_cols_stage<BN>(cols, p, b, n0, NW * 64);  // visible after the first barrier
-  Fwd16Dma<BM, BN, NW> dma;
-  dma.init(p, t_begin, b, n0, wid, lane);
-  const int my_pieces = dma.per_wave();
-#pragma unroll
-  for (int j = 0; j < NSTAGE - 1; ++j) dma.issue(p, smem + j * STAGE, t_end, nK, b);
-
-  int gs = 0;  // stages consumed so far (global over the tiles)
-  for (int st = t_begin; st < t_end; ++st) {
-    const int s0 = fwd_tile_s0<BM>(st, p.S);
-    f32x4 acc[TM][TN];
-#pragma unroll
-    for (int m = 0; m < TM; ++m)
-#pragma unroll
-      for (int n = 0; n < TN; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    for (int kc = 0; kc < nK; ++kc, ++gs) {
-      // stage gs must have landed; later stages may stay in flight (loads
-      // retire in order, so stores issued after them need not be waited for)
-      if (NSTAGE == 2)
-        wait_vmcnt<0>();
-      else
-        wait_vmcnt_dyn(min(dma.issued - (gs + 1), NSTAGE - 2) * my_pieces);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      barrier_raw();  // stage gs landed for every wave; every wave is done reading gs-1
-      dma.issue(p, smem + ((gs + NSTAGE - 1) % NSTAGE) * STAGE, t_end, nK, b);
-      Frag16<TM, TN> f;
-      fwd16_read<TM, TN, BM>(f, smem + (gs % NSTAGE) * STAGE, wm, wn, lr, coh, col);
-      fwd16_mfma<TM, TN>(acc, f);
-    }
-    fwd_tile_epilogue<WM, WN, TM, TN>(p, ln, acc, scale, b, s0, st * BM, nt, red, cols);
-  }
-  fwd_colsum_epilogue<WM, WN, TM, TN>(p, ln, b, sc, n0, red);
-}
-
 // ------------------------------------------ 3xf16, transposed accumulators
 // The same GEMM with the roles of the operands swapped: MFMA-M = labels (R
 // rows), MFMA-N = samples (eps rows).  A lane then holds 4 consecutive labels
@@ -776,7 +616,7 @@ MPV_DEV void pk_fma2_acc_bc(f32x2 p, f32x2 q, f32x2 r, f32x2& sp, f32x2& sn) {
 // Every element is finite (R pad rows are zero, eps rows are clamped), so
 // weighting instead of selecting is exact.
 template <int WL, int WS, int TL, int TS, int BMT = WS * TS * 16, bool RED_IN_RING = false,
-          int EPI_BLOCKS = kEpiSampleBlocks, bool UNROLL_L = false, bool PUBLISH = true, int CQ = 1>
+          int EPI_BLOCKS = kEpiSampleBlocks, bool PUBLISH = true, int CQ = 1>
 MPV_DEV void fwd_tile_epilogue_t(const FwdParams& p, f32x4 (&acc)[TL][TS], float scale,
                                  int b, int s0, int s_own, int nt, float* red, float* cacc,
                                  const float* cols, bool soft_any, int sbo = -1) {
@@ -800,8 +640,7 @@ MPV_DEV void fwd_tile_epilogue_t(const FwdParams& p, f32x4 (&acc)[TL][TS], float
   // unrolls fully without spilling, and the forward measures the same: C4
   // 13.28 / 13.25 vs 13.33 / 13.20 ms, so the rotation's moves are not on the
   // critical path)
-  constexpr int kUnrollL = UNROLL_L ? TL : 1;
-#pragma unroll kUnrollL
+#pragma unroll 1
   for (int m = 0; m < TL; ++m) {
     f32x4 am[TS];
 #pragma unroll
@@ -976,7 +815,7 @@ MPV_DEV void fwd_tile_epilogue_t(const FwdParams& p, f32x4 (&acc)[TL][TS], float
   // label-branch update of one 16-lane row with the pad in place, with no
   // inline asm at all, with ds_bpermute sums instead of permlanes, and without
   // the T stash; only one workgroup per CU removes it.  DESIGN.md section 3,
-  // "the round-3 lost update", tools/studies/race_study.sh.)
+  // "the round-3 lost update".)
   __builtin_amdgcn_sched_barrier(0);
   asm volatile("s_nop 1" ::: "memory");
   __builtin_amdgcn_sched_barrier(0);
@@ -1342,7 +1181,7 @@ MPV_DEV void fwd16b_epilogue_parts(const FwdParams& p, f32x4 (&acc)[TL][TSW], fl
   for (int m = 0; m < TL; ++m)
 #pragma unroll
     for (int n = 0; n < H; ++n) a[m][n] = acc[m][PART * H0 + n];
-  fwd_tile_epilogue_t<4, 2, TL, H, BM, PART == 0, kFwdBEpi, kFwdBUnroll, PART == NP - 1, kFwdBCQ>(
+  fwd_tile_epilogue_t<4, 2, TL, H, BM, PART == 0, kFwdBEpi, PART == NP - 1, kFwdBCQ>(
       p, a, scale, b, s0, s_own, nt, red, cacc, cols, soft_any, sbo + PART * H0);
   if constexpr (PART + 1 < NP)
     fwd16b_epilogue_parts<PART + 1, NP, TL, TSW, BM>(p, acc, scale, b, s0, s_own, nt, red, cacc, cols,
@@ -1440,10 +1279,7 @@ __global__ __launch_bounds__(512, 1) void probit_fwd16b_kernel(FwdParams p) {
 // ranking mean, :207-208 total) from the per-row statistics, by ONE block of
 // kFinalThreads threads.  row(b, v) yields row b's (M, Z, M_x, Z_x, c, c_x);
 // both finalize variants sum in this same order.
-#ifndef MPV_FINAL_THREADS
-#define MPV_FINAL_THREADS 1024
-#endif
-constexpr int kFinalThreads = MPV_FINAL_THREADS;
+constexpr int kFinalThreads = 1024;
 template <class Row>
 MPV_DEV void finalize_scalars(const mpv_final_args& a, int B, float S_total, Row row) {
   __shared__ float red[16 * 5];
@@ -1687,9 +1523,9 @@ static FwdPlan plan_fwd(const mpv_shape* s, int gemm) {
   // tile configurations: 0 = 48 labels (L <= 48), 1 = 96 labels (fp32 mode,
   // L <= 96; 3xf16: the transposed 96 x 128 tile), 2 = 128 labels (transposed
   // 3xf16 tile, or the fp32 64 x 64 waves), 3 = 256 labels (3xf16, L > 128).
-  // (Round 2 measured the 3xf16 96-label tile of probit_fwd16, MFMA-layout
-  // accumulators, slower at C3 than the 128-label transposed tile; the
-  // transposed 96-label tile is the one used now.)
+  // (Round 2 measured a 3xf16 96-label tile with MFMA-layout accumulators
+  // slower at C3 than the 128-label transposed tile; the transposed 96-label
+  // tile is the one used now.)
   const bool f16 = gemm == MPV_GEMM_F16X3;
   pl.cfg = s->L <= 48 ? 0 : (s->L <= 96 ? 1 : ((f16 && s->L > 128) ? 3 : 2));
   // (the 256 x 256 tile streams whole tiles: S >= 256, Fwd16DmaLin.
@@ -1698,8 +1534,7 @@ static FwdPlan plan_fwd(const mpv_shape* s, int gemm) {
   const char* tile_env = std::getenv("MPVAE_FWD_TILE");
   const bool tile128 = tile_env != nullptr && std::strcmp(tile_env, "256x128") == 0;
   pl.BM = (f16 && pl.cfg == 0) ? kFwd48BM
-                               : ((f16 && pl.cfg == 3 && kFwdB && !tile128 && s->S_local >= 256) ? 256
-                                                                                                 : 128);
+                               : ((f16 && pl.cfg == 3 && !tile128 && s->S_local >= 256) ? 256 : 128);
   pl.BN = pl.cfg == 0 ? 48 : (pl.cfg == 1 ? 96 : (pl.cfg == 2 ? 128 : 256));
   pl.nNt = (int)cdiv(s->L, pl.BN);
   pl.nSt = (int)cdiv(s->S_local, pl.BM);

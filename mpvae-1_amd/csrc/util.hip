@@ -484,18 +484,9 @@ constexpr float kNoiseScale = 4096.0f;
 // call when z % 4 == 0, else words of two calls), stored as two 16-B vectors.
 // Planes narrower than 8 x blockDim columns give each row cols/8 threads and
 // the block several rows at once.
-#ifndef MPV_NOISE_ROWS
-#define MPV_NOISE_ROWS 16
-#endif
-#ifndef MPV_NOISE_NT
-#define MPV_NOISE_NT 0  // nontemporal plane stores: 1.69 -> 2.61 ms at C4 (r06_noise_ab.json)
-#endif
-constexpr int kNoiseRows = MPV_NOISE_ROWS;  // plane rows per block (1: 2.08 ms, 4: 1.99, 16: 1.93 at C4; 8, 32: as 16)
+constexpr int kNoiseRows = 16;  // plane rows per block (1: 2.08 ms, 4: 1.99, 16: 1.93 at C4; 8, 32: as 16)
 constexpr int kNoiseCols = 8;   // plane columns per thread (4: 1.78 ms, 8: 1.69 ms at C4)
-#ifndef MPV_NOISE_PASSES
-#define MPV_NOISE_PASSES 2
-#endif
-constexpr int kNoisePasses = MPV_NOISE_PASSES;  // narrow planes: row passes per block
+constexpr int kNoisePasses = 2;  // narrow planes: row passes per block
 // Plane columns the noise kernel writes: z rounded up to the GEMMs' 32-wide K
 // slices (zeros past z).  Columns beyond that (the dR tile's padding) are left
 // as they are: the forward GEMM never reads them, and in the dR GEMM they only
@@ -588,13 +579,9 @@ MPV_DEV void noise16_row(const mpv_split16& out, int S, int B, int z, int64_t s_
                    (short)h[4], (short)h[5], (short)h[6], (short)h[7]};
     const s16x8 lv{(short)l[0], (short)l[1], (short)l[2], (short)l[3],
                    (short)l[4], (short)l[5], (short)l[6], (short)l[7]};
-#if MPV_NOISE_NT
-    __builtin_nontemporal_store(hv, reinterpret_cast<s16x8*>(out.data + o));
-    __builtin_nontemporal_store(lv, reinterpret_cast<s16x8*>(out.data + o + kLoOff));
-#else
+    // plain stores (nontemporal ones measured slower: DESIGN.md section 3)
     *reinterpret_cast<s16x8*>(out.data + o) = hv;
     *reinterpret_cast<s16x8*>(out.data + o + kLoOff) = lv;
-#endif
   }
 }
 

@@ -80,7 +80,7 @@ def kernel_probit_prob(t32, base32, form):
     for ck in c[2:]:
         p = _fma(t, p.to(F64), ck)
     z64 = zq.to(F64)
-    # om = 1 - erfc as one fma of the unrounded product (MPV_OM_FMA)
+    # om = 1 - erfc as one fma of the unrounded product (as both kernels form it)
     if form == "p":
         a = (-z64 * z64 + p.to(F64)).to(F32)
         om = _fma(-t, torch.exp2(a.to(F64)).to(F32).to(F64), 1.0)

@@ -106,7 +106,7 @@ def main(src, dst, tag):
                 # MFMA-busy cycles per SIMD (1024 SIMDs) over the kernel's GPU cycles
                 # (GRBM_GUI_ACTIVE summed over the 8 XCDs)
                 out["kernels"][k]["mfma_busy_frac"] = mbusy[k] / 1024.0 / (grbm[k] / 8.0)
-    # aliases under the timing tags bench.py reports (e.g. probit_fwd16 -> probit_fwd)
+    # aliases under the timing tags bench.py reports (e.g. probit_fwd16b -> probit_fwd)
     for k in list(out["kernels"]):
         t = tag_of(k)
         if t is not None and t not in out["kernels"]:
