@@ -4,13 +4,18 @@
 // (v_mfma_f32_16x16x32_f16, fp32 accumulate, ~fp32 accuracy, see mpv_common.h),
 // operand tiles streamed global->LDS by LDS-DMA (global_load_lds_dwordx4) into
 // a double-buffered, XOR-swizzled image; accumulators transposed (MFMA-M =
-// labels).  Every 3xf16 tile is 8 waves, one workgroup per CU (launch_fwd):
-//   probit_fwd16t_kernel  even sample split: 48 labels x 256 samples (L <= 48)
-//                         and 96 labels x 128 samples (48 < L <= 96).
-//   probit_fwd16a_kernel  asymmetric 80 / 48 sample split: 128 labels x 128
-//                         samples (96 < L <= 128), and 256 labels x 128 samples
-//                         (L > 128 with S < 256, or MPVAE_FWD_TILE=256x128).
-//   probit_fwd16b_kernel  256 labels x 256 samples (L > 128 and S >= 256: the
+// labels).
+//   probit_fwd16_kernel   every 3xf16 tile: 8 waves, one workgroup per CU, one
+//                         tile loop (fwd16_tiles) instantiated from a tile
+//                         descriptor (pick_fwd_tile):
+//     Fwd16tTile48x256, Fwd16tTile96x128    even sample split: 48 labels x 256
+//                         samples (L <= 48), 96 labels x 128 samples
+//                         (48 < L <= 96).
+//     Fwd16aTile128x128, Fwd16aTile256x128  asymmetric 80 / 48 sample split:
+//                         128 labels x 128 samples (96 < L <= 128), and 256
+//                         labels x 128 samples (L > 128 with S < 256, or
+//                         MPVAE_FWD_TILE=256x128).
+//     Fwd16bTile256x256   256 labels x 256 samples (L > 128 and S >= 256: the
 //                         C4 / C5 tile).
 //   probit_fwd_kernel     the same product with exact fp32 MFMA
 //                         (v_mfma_f32_16x16x4_f32) on fp32 operands
@@ -427,7 +432,7 @@ __global__ MPV_NO_PK_FP32 __launch_bounds__(WM* WN * 64) void probit_fwd_kernel(
 
 // ------------------------------------------------------ 3xf16 mainloop
 // The K axis (z) is streamed in stages of 32 (one MFMA k-step) through a ring
-// of NSTAGE LDS stage images filled by LDS-DMA (global_load_lds_dwordx4).  The
+// of kFwdRing LDS stage images filled by LDS-DMA (global_load_lds_dwordx4).  The
 // split operands are chunked (mpv_split16): the hi and lo halves of a row's
 // 32-element K slice are one 128-B line, and a stage image row is exactly that
 // line: [hi 64 B | lo 64 B].  Image: BM eps rows (A), then BN R rows (B).  One
@@ -438,6 +443,8 @@ __global__ MPV_NO_PK_FP32 __launch_bounds__(WM* WN * 64) void probit_fwd_kernel(
 // lane-linearly, so the swizzle goes on the per-lane SOURCE address.
 constexpr int kKC = 32;     // K elements per stage
 constexpr int kRowB = 128;  // bytes per stage-image row (hi + lo)
+constexpr int kFwdRing = 2;  // stage images: one read by the MFMAs while the DMA fills the other
+constexpr int kFwd16Threads = 512;  // every 3xf16 tile is 8 waves
 
 // First sample row of s-tile st.  With S >= BM the last tile is shifted back
 // to end at S (its leading rows, already owned by tile st-1, are recomputed
@@ -457,12 +464,10 @@ template <int BM, int BN, int NW>
 struct Fwd16Dma {
   static constexpr int GA = BM / 8, GB = BN / 8;  // pieces per operand image
   static constexpr int JA = (GA + NW - 1) / NW, JB = (GB + NW - 1) / NW;
-  static constexpr bool EVEN = GA % NW == 0 && GB % NW == 0;
   const char* a_base;  // eps rows of the current tile
   const char* b_base;  // R rows of the label tile
   uint32_t offa[JA], offb[JB];
   int tile, kc;  // next stage to issue
-  int issued;    // stages issued so far
   int wid;
 
   MPV_DEV void init(const FwdParams& p, int t0, int b, int n0, int wid_, int lane) {
@@ -483,19 +488,12 @@ struct Fwd16Dma {
     }
     tile = t0;
     kc = 0;
-    issued = 0;
     set_tile(p, b);
   }
 
   MPV_DEV void set_tile(const FwdParams& p, int b) {
     const int64_t o = ((int64_t)b * p.S + fwd_tile_s0<BM>(tile, p.S)) * p.eps16.ld;
     a_base = reinterpret_cast<const char*>(p.eps16.data + o);
-  }
-
-  // pieces this wave streams per stage
-  MPV_DEV int per_wave() const {
-    if (EVEN) return JA + JB;
-    return (GA - wid + NW - 1) / NW + (GB - wid + NW - 1) / NW;
   }
 
   // base: wave-uniform (SGPRs); off: per-lane byte offset (inline-asm DMA, see lds_dma16)
@@ -517,12 +515,146 @@ struct Fwd16Dma {
       const int pc = wid + j * NW;
       if (GB % NW == 0 || pc < GB) piece(b_base + kb, offb[j], dst + BM * kRowB + pc * 1024);
     }
-    ++issued;
     if (++kc == nK) {
       kc = 0;
       if (++tile < tile_end) set_tile(p, b);
     }
   }
+};
+
+// Fwd16Dma for S >= BM (no row clamp), same interface: the pieces of one
+// operand image are 32 rows apart, and (r >> 1) & 7 repeats every 16 rows, so
+// every piece of an image has the same per-lane offset from its
+// (wave-uniform) row base -- two offset VGPRs instead of JA + JB.
+template <int BM, int BN, int NW>
+struct Fwd16DmaLin {
+  static constexpr int GA = BM / 8, GB = BN / 8;
+  static constexpr int JA = GA / NW, JB = GB / NW;
+  static_assert(GA % NW == 0 && GB % NW == 0, "pieces split evenly over the DMA waves");
+  const char* a_base;  // eps rows of the current tile, this wave's first piece
+  const char* b_base;  // R rows of the label tile, this wave's first piece
+  int64_t a_step, b_step;  // bytes between a wave's consecutive pieces (NW * 8 rows)
+  uint32_t offa, offb;
+  int tile, kc, wid;
+
+  MPV_DEV void init(const FwdParams& p, int t0, int b, int n0, int wid_, int lane) {
+    wid = wid_;
+    const int64_t lda = p.eps16.ld, ldb = p.R16.ld;
+    const int prow = lane >> 3, u_lds = lane & 7;
+    a_step = (int64_t)NW * 8 * lda * 2;
+    b_step = (int64_t)NW * 8 * ldb * 2;
+    b_base = reinterpret_cast<const char*>(p.R16.data + ((int64_t)n0 + wid * 8) * ldb);
+    offa = (uint32_t)(prow * lda * 2) + (uint32_t)((u_lds ^ (((wid * 8 + prow) >> 1) & 7)) * 16);
+    offb = (uint32_t)(prow * ldb * 2) + (uint32_t)((u_lds ^ (((wid * 8 + prow) >> 1) & 7)) * 16);
+    tile = t0;
+    kc = 0;
+    set_tile(p, b);
+  }
+  MPV_DEV void set_tile(const FwdParams& p, int b) {
+    const int64_t o = ((int64_t)b * p.S + fwd_tile_s0<BM>(tile, p.S) + wid * 8) * p.eps16.ld;
+    a_base = reinterpret_cast<const char*>(p.eps16.data + o);
+  }
+  MPV_DEV void issue(const FwdParams& p, char* dst, int tile_end, int nK, int b) {
+    if (tile >= tile_end) return;
+    const int kb = kc * kRowB;
+#pragma unroll
+    for (int j = 0; j < JA; ++j)
+      lds_dma16(a_base + kb + j * a_step, offa, lds_addr(dst + (wid + j * NW) * 1024));
+#pragma unroll
+    for (int j = 0; j < JB; ++j)
+      lds_dma16(b_base + kb + j * b_step, offb, lds_addr(dst + BM * kRowB + (wid + j * NW) * 1024));
+    if (++kc == nK) {
+      kc = 0;
+      if (++tile < tile_end) set_tile(p, b);
+    }
+  }
+};
+
+// ------------------------------------------------ 3xf16 tile descriptors
+// One per shipped tile (pick_fwd_tile).  Every tile is 8 waves, wave wid owning
+// label group wl = wid % WL (TL 16-label blocks) and sample group ws =
+// wid / WL; one workgroup per CU.  The sample groups of the first wave half
+// (wid < 4) own TSA 16-sample blocks each, those of the second half TSB, and
+// the second half issues the stage DMA at static priority 1 (the other half
+// starts its MFMAs at the barrier).
+//   BM, BN       samples and labels per tile
+//   LDS_MIN      the LDS size at least (one workgroup per CU whatever the
+//                register count: packed fp32 VALU beside another workgroup's
+//                waves is not used, see MPV_NO_PK_FP32)
+//   Dma          the DMA cursor (4 waves stream)
+//   CQ           column-sum slots per 16-lane row
+//   EPI_BLOCKS   sample blocks between the label loop's scheduling barriers
+//   EPI_PART     sample blocks per epilogue part (0: the epilogue runs whole)
+//   RED_IN_RING  the row-statistics exchange (red) lives in the stage image
+//                the tile's last K stage was read from
+//   AHEAD        a stage's eps fragments are read one block ahead of their
+//                products (fwd16_stage_ahead), not all up front
+//
+// fwd16t: even sample split.  48 labels x kFwd48BM samples (L <= 48) and 96
+// labels x 128 samples (48 < L <= 96: 8 waves of 48 labels x 32 samples).
+struct Fwd16tTile48x256 {
+  static constexpr int WL = 1, WS = 8, TL = 3, TSA = kFwd48BM / 128, TSB = TSA;
+  static constexpr int BM = kFwd48BM, BN = 48, LDS_MIN = 82 * 1024;
+  using Dma = Fwd16Dma<BM, BN, 4>;
+  static constexpr int CQ = 1, EPI_BLOCKS = kEpiSampleBlocks, EPI_PART = 0;
+  static constexpr bool RED_IN_RING = false, AHEAD = false;
+};
+struct Fwd16tTile96x128 {
+  static constexpr int WL = 2, WS = 4, TL = 3, TSA = 2, TSB = 2;
+  static constexpr int BM = 128, BN = 96, LDS_MIN = 0;
+  using Dma = Fwd16Dma<BM, BN, 4>;
+  static constexpr int CQ = 1, EPI_BLOCKS = kEpiSampleBlocks, EPI_PART = 0;
+  static constexpr bool RED_IN_RING = false, AHEAD = false;
+};
+// fwd16a: asymmetric sample split, (TL * 64) labels x 128 samples (4 label
+// groups x 2 sample groups).  The 128 samples are split unevenly between the
+// two waves of each SIMD: waves 0-3 own TSA 16-sample blocks, waves 4-7 TSB
+// (< TSA) and stream every stage's DMA at static priority 1.  With an even
+// split the DMA half runs its 48 MFMAs after ~800 cycles of DMA issue while
+// the other half is already done and waits at the barrier; here the DMA half
+// has less MFMA work, so its DMA issue hides under the other half's longer
+// MFMA phase.
+//
+// 128 labels x 128 samples (96 < L <= 128), 8 waves, asymmetric 80 / 48
+// sample split (C3 before the 96-label tile: forward 0.187 -> 0.181 ms
+// against the even 64 / 64 split).  A
+// 4-wave version of this tile (64 x 64 per wave, two workgroups per CU)
+// ran 0.031 ms faster at C3 but was not repeatable: 10-13 % of its
+// launches at C3 differed in one label-branch row statistic of a
+// 16-sample block (never with one workgroup per CU, the same code padded
+// to 81 KB of LDS; DESIGN.md section 4, tools/repeat_probe.py)
+struct Fwd16aTile128x128 {
+  static constexpr int WL = 4, WS = 2, TL = 2, TSA = 5, TSB = 3;
+  static constexpr int BM = 128, BN = 128, LDS_MIN = 0;
+  using Dma = Fwd16Dma<BM, BN, 4>;
+  static constexpr int CQ = 1, EPI_BLOCKS = kEpiSampleBlocks, EPI_PART = 0;
+  static constexpr bool RED_IN_RING = false, AHEAD = false;
+};
+// 256 labels x 128 samples (L > 128 with S < 256, or MPVAE_FWD_TILE=256x128)
+struct Fwd16aTile256x128 {
+  static constexpr int WL = 4, WS = 2, TL = 4, TSA = 5, TSB = 3;
+  static constexpr int BM = 128, BN = 256, LDS_MIN = 0;
+  using Dma = Fwd16Dma<BM, BN, 4>;
+  static constexpr int CQ = 1, EPI_BLOCKS = kEpiSampleBlocks, EPI_PART = 0;
+  static constexpr bool RED_IN_RING = false, AHEAD = false;
+};
+// fwd16b: 256 labels x 256 samples, the C4 / C5 tile.
+// probit_fwd16a with twice the samples per tile (dispatched for L > 128 and
+// S >= 256; C4 forward 13.6 -> 12.5 ms, round 6): the stage image streams
+// (256 + 256) rows for 256 x 256 x 32 products instead of (256 + 128) for
+// 256 x 128 x 32 (a third fewer operand bytes per product), and each wave's
+// fragment reads cover 64 x TS*16 products.  The accumulators (TL x TSW
+// blocks) leave room for all R fragments of a stage but not all eps ones, so
+// the eps fragments of one 16-sample block are read right before its
+// products (one block ahead).  The row-statistics exchange (red, 24 KB)
+// lives in the stage image the tile's last K stage was read from; the
+// epilogue runs in parts of kFwdBPart sample blocks.
+struct Fwd16bTile256x256 {
+  static constexpr int WL = 4, WS = 2, TL = 4, TSA = kFwdBA, TSB = 16 - kFwdBA;
+  static constexpr int BM = 256, BN = 256, LDS_MIN = 0;
+  using Dma = Fwd16DmaLin<BM, BN, 4>;  // whole tiles only: S >= 256
+  static constexpr int CQ = kFwdBCQ, EPI_BLOCKS = kFwdBEpi, EPI_PART = kFwdBPart;
+  static constexpr bool RED_IN_RING = true, AHEAD = true;
 };
 
 // ------------------------------------------ 3xf16, transposed accumulators
@@ -538,7 +670,7 @@ struct FragT {
   s16x8 rh[TL], rl[TL], eh[TS], el[TS];  // R (labels) and eps (samples), hi / lo
 };
 
-template <int WL, int TL, int TS, int BM>
+template <int TL, int TS, int BM>
 MPV_DEV void fwd16t_read(FragT<TL, TS>& f, const char* base, int wl, int sbo, int lr, int coh,
                          int col) {
 #pragma unroll
@@ -556,7 +688,7 @@ MPV_DEV void fwd16t_read(FragT<TL, TS>& f, const char* base, int wl, int sbo, in
 }
 
 // The same products per accumulator in the same order (hi.hi, hi.lo, lo.hi),
-// issued term by term over all tiles: consecutive MFMAs see operands of one
+// placed term by term over all tiles: consecutive MFMAs see operands of one
 // kind (-0.75 % against accumulator by accumulator).
 template <int TL, int TS>
 MPV_DEV void fwd16t_mfma(f32x4 (&acc)[TL][TS], const FragT<TL, TS>& f) {
@@ -610,21 +742,91 @@ MPV_DEV void pk_fma2_acc_bc(f32x2 p, f32x2 q, f32x2 r, f32x2& sp, f32x2& sn) {
         : "+v"(sp), "+v"(sn) : "v"(p), "v"(q), "v"(r));
 }
 
-// acc[m][n][i] = t of sample (ws*TS+n)*16 + lr, label (wl*TL+m)*16 + 4*lg + i.
+// Does the workgroup's label tile hold soft (non 0/1) labels?  (uniform;
+// enables the two-log BCE path of the epilogue)
+template <int BN>
+MPV_DEV bool fwd_tile_soft(const FwdParams& p, int b, int n0, int nthreads) {
+  bool my_soft = false;
+  for (int i = threadIdx.x; i < BN; i += nthreads) {
+    const int l = n0 + i;
+    if (l < p.L) {
+      const float yv = p.y[(int64_t)b * p.L + l];
+      my_soft |= !(yv == 0.0f || yv == 1.0f);
+    }
+  }
+  return __builtin_amdgcn_readfirstlane(__syncthreads_or(my_soft)) != 0;
+}
+
+// What a workgroup of a transposed tile and its waves and lanes own, fixed
+// for the workgroup's life.  (Handed on by value: by reference the 128 x 128
+// and 256 x 256 tiles spill one more SGPR each and the 256 x 128 tile takes
+// two more VGPRs.)
+struct Fwd16Ctx {
+  int b, sc, nt, n0;     // batch row, s-chunk, label tile and its first label
+  int wid, wl, ws;       // wave (uniform), its label and sample group
+  int lr, lg;            // lane & 15, lane >> 4
+  int coh, col;          // byte offsets of the lane's hi / lo unit in a (swizzled) image row
+  float scale;           // t = acc * scale
+  int nK;                // K stages per tile
+  int t_begin, t_end;    // the workgroup's s-tiles
+  bool soft_any;         // fwd_tile_soft
+  float* cacc;           // LDS: column-sum slots [WS * CQ][BN][2]
+  const float* cols;     // LDS: label constants (fwd_cols_stage_t)
+};
+
+// Decodes the block, stages the label constants into `cols` and zeroes `cacc`.
+template <class Tile>
+MPV_DEV Fwd16Ctx fwd16_ctx(const FwdParams& p, float* cacc, float* cols) {
+  constexpr int WL = Tile::WL, BN = Tile::BN, CACC = Tile::WS * Tile::CQ * BN * 2;
+  Fwd16Ctx c;
+  int g;
+  decode_block(blockIdx.x, p.B * p.nSc, p.nNt, g, c.nt);
+  c.b = g / p.nSc, c.sc = g % p.nSc;
+  c.n0 = c.nt * BN;
+  const int tid = threadIdx.x, lane = tid & 63;
+  c.wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  c.wl = c.wid % WL, c.ws = c.wid / WL;
+  c.lr = lane & 15, c.lg = lane >> 4;
+  c.scale = 1.0f / (*p.eps16.scale * *p.R16.scale);
+  c.nK = (p.z + kKC - 1) / kKC;
+  const int sw = (c.lr >> 1) & 7;
+  c.coh = (c.lg ^ sw) << 4, c.col = ((4 + c.lg) ^ sw) << 4;
+  c.t_begin = c.sc * p.tps, c.t_end = min(p.nSt, (c.sc + 1) * p.tps);
+  fwd_cols_stage_t<BN>(cols, p, c.b, c.n0, kFwd16Threads);
+  for (int i = tid; i < CACC; i += kFwd16Threads) cacc[i] = 0.0f;
+  c.soft_any = fwd_tile_soft<BN>(p, c.b, c.n0, kFwd16Threads);
+  c.cacc = cacc, c.cols = cols;
+  return c;
+}
+
+// acc[m][n][i] = t of sample (sbo+n)*16 + lr, label (wl*TL+m)*16 + 4*lg + i.
 // Masks are carried as 0/1 float weights (VGPRs) rather than lane masks: the
 // 16 per-label masks of a label group would otherwise pin ~40 SGPRs and spill.
 // Every element is finite (R pad rows are zero, eps rows are clamped), so
 // weighting instead of selecting is exact.
-template <int WL, int WS, int TL, int TS, int BMT = WS * TS * 16, bool RED_IN_RING = false,
-          int EPI_BLOCKS = kEpiSampleBlocks, bool PUBLISH = true, int CQ = 1>
-MPV_DEV void fwd_tile_epilogue_t(const FwdParams& p, f32x4 (&acc)[TL][TS], float scale,
-                                 int b, int s0, int s_own, int nt, float* red, float* cacc,
-                                 const float* cols, bool soft_any, int sbo = -1) {
-  constexpr int NT = WL * WS * 64, BM = BMT, BN = WL * TL * 16;
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int wl = wid % WL, ws = wid / WL, lr = lane & 15, lg = lane >> 4;
-  if (sbo < 0) sbo = ws * TS;  // first 16-sample block of this wave
-  const int S = p.S, B = p.B, L = p.L, n0 = nt * BN;
+// The TS sample blocks from sbo (the wave's first 16-sample block of this
+// call) on.  FIRST / LAST: the first / last call on a tile (the epilogue of a
+// tile may run in parts): the first waits for the ring image `red` aliases,
+// the last publishes the tile's row statistics.
+template <class Tile, int TS, bool FIRST = true, bool LAST = true>
+MPV_DEV void fwd_tile_epilogue_t(const FwdParams& p, const Fwd16Ctx c, f32x4 (&acc)[Tile::TL][TS],
+                                 int s0, int s_own, int sbo, float* red) {
+  constexpr int WL = Tile::WL, TL = Tile::TL, BM = Tile::BM, BN = Tile::BN, NT = kFwd16Threads;
+  const int tid = threadIdx.x, lr = c.lr, lg = c.lg;
+  // The wave's label / sample group per lane (in the even split its first
+  // sample block too), and the tile's first label from nt, not the context's
+  // wave-uniform wl / ws and its n0: with those the label loop keeps more in
+  // SGPRs than it has (SGPR spills of the five tiles 4 / 4 / 9 / 10 / 37 ->
+  // 7 / 7 / 10 / 16 / 40, VGPR spills of the 256 x 256 tile 9 -> 13)
+  const int wid = tid >> 6, wl = wid % WL, ws = wid / WL;
+  if constexpr (Tile::TSA == Tile::TSB) {
+    static_assert(TS == Tile::TSA, "the even-split tiles run the epilogue whole");
+    sbo = ws * TS;
+  }
+  const int S = p.S, B = p.B, L = p.L, b = c.b, nt = c.nt, n0 = nt * BN;
+  const float scale = c.scale;
+  float* cacc = c.cacc;
+  const float* cols = c.cols;
   f32x2 sl[TS], sp[TS], sn[TS];  // per sample: log-prob, P, N (label .x / feature .y branch)
 #pragma unroll
   for (int n = 0; n < TS; ++n) sl[n] = sp[n] = sn[n] = splat2(0.0f);
@@ -745,7 +947,7 @@ MPV_DEV void fwd_tile_epilogue_t(const FwdParams& p, f32x4 (&acc)[TL][TS], float
       // the product of 4 stays >= 5e-26, far from underflow
       const f32x2 q4 = (q[0] * q[1]) * (q[2] * q[3]);
       f32x2 lp = f32x2{__builtin_amdgcn_logf(q4.x), __builtin_amdgcn_logf(q4.y)};
-      if (soft_any) {
+      if (c.soft_any) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const float y = y4[i];
@@ -767,7 +969,7 @@ MPV_DEV void fwd_tile_epilogue_t(const FwdParams& p, f32x4 (&acc)[TL][TS], float
         ce[i] = pk_fma(splat2(wr), E4[i], ce[i]);  // column sums of E over the wave's samples
       }
       // kEpiSampleBlocks samples at a time: bounded live ranges vs more independent chains
-      if ((n + 1) % EPI_BLOCKS == 0) __builtin_amdgcn_sched_barrier(0);
+      if ((n + 1) % Tile::EPI_BLOCKS == 0) __builtin_amdgcn_sched_barrier(0);
     }
     // column sums of these 4 labels over the wave's samples: 16-lane trees
     // (8 chains step-major), lane 15 of each row accumulates into the
@@ -778,7 +980,7 @@ MPV_DEV void fwd_tile_epilogue_t(const FwdParams& p, f32x4 (&acc)[TL][TS], float
       cs[2 * i] = ce[i].x;
       cs[2 * i + 1] = ce[i].y;
     }
-    if (CQ == 4) {
+    if (Tile::CQ == 4) {
       // two DPP steps: the last lane of each quad holds the quad's sum, and
       // the four quads of a row accumulate into their own slots (summed
       // once per workgroup by fwd16t_colpart)
@@ -834,14 +1036,14 @@ MPV_DEV void fwd_tile_epilogue_t(const FwdParams& p, f32x4 (&acc)[TL][TS], float
   sum_lanegroups_n<TS * 6>(v);  // all chains step-major
   // red aliases the stage image the last K stage was read from: every wave
   // is past its fragment reads once all have met here
-  if (RED_IN_RING) lds_barrier();
+  if (Tile::RED_IN_RING && FIRST) lds_barrier();
   if (lg == 0) {
 #pragma unroll
     for (int n = 0; n < TS; ++n)
 #pragma unroll
       for (int k = 0; k < 6; ++k) red[(wl * BM + (sbo + n) * 16 + lr) * 6 + k] = v[n * 6 + k];
   }
-  if (!PUBLISH) return;  // a later call on the tile's other sample blocks publishes
+  if (!LAST) return;  // a later call on the tile's other sample blocks publishes
   lds_barrier();
   for (int r = tid; r < BM; r += NT) {
     const int s = s0 + r;
@@ -859,16 +1061,16 @@ MPV_DEV void fwd_tile_epilogue_t(const FwdParams& p, f32x4 (&acc)[TL][TS], float
 }
 
 // Column partials of a transposed-tile workgroup -> colpart[sc, ., b, n0 ...]
-template <int WS, int BN, int CQ = 1>
-MPV_DEV void fwd16t_colpart(const FwdParams& p, const float* cacc, int b, int sc, int n0,
-                            int nthreads) {
+// (summing cacc's NSLOT slots per label)
+template <int NSLOT, int BN>
+MPV_DEV void fwd16t_colpart(const FwdParams& p, const float* cacc, int b, int sc, int n0) {
   lds_barrier();
-  for (int c = threadIdx.x; c < BN; c += nthreads) {
+  for (int c = threadIdx.x; c < BN; c += kFwd16Threads) {
     const int l = n0 + c;
     if (l < p.L) {
       float e = 0.f, x = 0.f;
 #pragma unroll
-      for (int w = 0; w < WS * CQ; ++w) {
+      for (int w = 0; w < NSLOT; ++w) {
         e += cacc[(w * BN + c) * 2 + 0];
         x += cacc[(w * BN + c) * 2 + 1];
       }
@@ -878,265 +1080,13 @@ MPV_DEV void fwd16t_colpart(const FwdParams& p, const float* cacc, int b, int sc
   }
 }
 
-// Does the workgroup's label tile hold soft (non 0/1) labels?  (uniform;
-// enables the two-log BCE path of the epilogue)
-template <int BN>
-MPV_DEV bool fwd_tile_soft(const FwdParams& p, int b, int n0, int nthreads) {
-  bool my_soft = false;
-  for (int i = threadIdx.x; i < BN; i += nthreads) {
-    const int l = n0 + i;
-    if (l < p.L) {
-      const float yv = p.y[(int64_t)b * p.L + l];
-      my_soft |= !(yv == 0.0f || yv == 1.0f);
-    }
-  }
-  return __builtin_amdgcn_readfirstlane(__syncthreads_or(my_soft)) != 0;
-}
-
-// The transposed 3xf16 tile with an even sample split (launch_fwd: 96 labels x
-// 128 samples for 48 < L <= 96: 8 waves of 48 labels x 32 samples), 2-stage
-// ring.  The waves of the second half issue the stage DMA at static priority 1
-// (the other half starts its MFMAs at the barrier).
-// LDS_MIN: the LDS size at least (one workgroup per CU whatever the register
-// count: packed fp32 VALU beside another workgroup's waves is not used, see
-// MPV_NO_PK_FP32).
-template <int WL, int WS, int TL, int TS, int NSTAGE, int LDS_MIN = 0>
-__global__ __launch_bounds__(WL* WS * 64, 8 / (WL * WS)) void probit_fwd16t_kernel(FwdParams p) {
-  constexpr int NW = WL * WS;
-  constexpr int BM = WS * TS * 16, BN = WL * TL * 16;  // samples, labels
-  constexpr int STAGE = (BM + BN) * kRowB;
-  constexpr int RED = WL * BM * 6, CACC = WS * BN * 2;  // floats
-  constexpr int LDS = NSTAGE * STAGE + (RED + CACC + kColsT * BN) * 4;
-  __shared__ __attribute__((aligned(1024))) char smem[LDS > LDS_MIN ? LDS : LDS_MIN];
-  float* red = reinterpret_cast<float*>(smem + NSTAGE * STAGE);
-  float* cacc = red + RED;
-  float* cols = cacc + CACC;
-
-  int g, nt;
-  decode_block(blockIdx.x, p.B * p.nSc, p.nNt, g, nt);
-  const int b = g / p.nSc, sc = g % p.nSc;
-  const int n0 = nt * BN;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wl = wid % WL, ws = wid / WL;
-  const int lr = lane & 15, lg = lane >> 4;
-
-  const float scale = 1.0f / (*p.eps16.scale * *p.R16.scale);
-  const int nK = (p.z + kKC - 1) / kKC;
-  const int sw = (lr >> 1) & 7;
-  const int coh = (lg ^ sw) << 4, col = ((4 + lg) ^ sw) << 4;
-  const int t_begin = sc * p.tps, t_end = min(p.nSt, (sc + 1) * p.tps);
-
-  fwd_cols_stage_t<BN>(cols, p, b, n0, NW * 64);
-  for (int i = tid; i < CACC; i += NW * 64) cacc[i] = 0.0f;
-  const bool soft_any = fwd_tile_soft<BN>(p, b, n0, NW * 64);
-  constexpr int NWD = NW / 2;  // DMA-issuing waves: the prio-1 half
-  const bool dmaw = wid >= NW / 2;
-  Fwd16Dma<BM, BN, NWD> dma;
-  dma.init(p, t_begin, b, n0, wid % NWD, lane);
-  if (dmaw) {
-#pragma unroll
-    for (int j = 0; j < NSTAGE - 1; ++j) dma.issue(p, smem + j * STAGE, t_end, nK, b);
-  }
-
-  int gs = 0;
-  // the second half of the waves loses every age arbitration on its SIMD;
-  // static priority (MI355X_MICROARCH.md, two waves per SIMD, item 4)
-  if (wid >= NW / 2) __builtin_amdgcn_s_setprio(1);
-  for (int st = t_begin; st < t_end; ++st) {
-    const int s0 = fwd_tile_s0<BM>(st, p.S);
-    f32x4 acc[TL][TS];
-#pragma unroll
-    for (int m = 0; m < TL; ++m)
-#pragma unroll
-      for (int n = 0; n < TS; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    for (int kc = 0; kc < nK; ++kc, ++gs) {
-      if (NSTAGE == 2)
-        wait_vmcnt<0>();
-      else
-        wait_vmcnt_dyn(min(dma.issued - (gs + 1), NSTAGE - 2) * dma.per_wave());
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      barrier_raw();  // stage gs landed for every wave; every wave is done reading gs-1
-      FragT<TL, TS> f;
-      if (dmaw) dma.issue(p, smem + ((gs + NSTAGE - 1) % NSTAGE) * STAGE, t_end, nK, b);
-      fwd16t_read<WL, TL, TS, BM>(f, smem + (gs % NSTAGE) * STAGE, wl, ws * TS, lr, coh, col);
-      fwd16t_mfma<TL, TS>(acc, f);
-    }
-    __builtin_amdgcn_s_setprio(0);
-    fwd_tile_epilogue_t<WL, WS, TL, TS>(p, acc, scale, b, s0, st * BM, nt, red, cacc, cols,
-                                        soft_any);
-    // back to the K-loop priorities
-    if (wid >= NW / 2)
-      __builtin_amdgcn_s_setprio(1);
-    else
-      __builtin_amdgcn_s_setprio(0);
-  }
-  fwd16t_colpart<WS, BN>(p, cacc, b, sc, n0, NW * 64);
-}
-
-// ------------------------- 3xf16, asymmetric sample split (probit_fwd16a)
-// The transposed 3xf16 tile for L > 48: (TL * 64) labels x 128 samples, 8
-// waves (4 label groups x 2 sample groups), 2-stage LDS-DMA ring, one
-// workgroup per CU.  The 128 samples are split unevenly between the two waves
-// of each SIMD: waves 0-3 own TSA 16-sample blocks, waves 4-7 TSB (< TSA) and
-// stream every stage's DMA at static priority 1.  With an even split the DMA half
-// runs its 48 MFMAs after ~800 cycles of DMA issue while the other half is
-// already done and waits at the barrier; here the DMA half has less MFMA
-// work, so its DMA issue hides under the other half's longer MFMA phase.
-// IS_A: waves 0-3 (TSA blocks); else waves 4-7 (TSB blocks, DMA).
-template <int TSW, bool IS_A, int TSA, int TSB, int TL>
-MPV_DEV void fwd16a_tiles(const FwdParams& p, char* smem, float* red, float* cacc,
-                          const float* cols, Fwd16Dma<128, TL * 64, 4>& dma, bool dmaw, int b, int nt,
-                          int t_begin, int t_end, int nK, bool soft_any, int wl, int sbo, int lr,
-                          int coh, int col, float scale, bool prio1) {
-  constexpr int WL = 4, BM = 128, NSTAGE = 2;
-  constexpr int STAGE = (BM + TL * 64) * kRowB;
-  int gs = 0;
-  for (int st = t_begin; st < t_end; ++st) {
-    const int s0 = fwd_tile_s0<BM>(st, p.S);
-    f32x4 acc[TL][TSW];
-#pragma unroll
-    for (int m = 0; m < TL; ++m)
-#pragma unroll
-      for (int n = 0; n < TSW; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int kc = 0; kc < nK; ++kc, ++gs) {
-      wait_vmcnt<0>();
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      barrier_raw();  // stage gs landed for every wave; every wave is done reading gs-1
-      if (dmaw) {
-        dma.issue(p, smem + ((__builtin_amdgcn_readfirstlane(gs) + NSTAGE - 1) % NSTAGE) * STAGE,
-                  t_end, nK, b);
-      }
-      FragT<TL, TSW> f;
-      fwd16t_read<WL, TL, TSW, BM>(f, smem + (gs % NSTAGE) * STAGE, wl, sbo, lr, coh, col);
-      fwd16t_mfma<TL, TSW>(acc, f);
-    }
-    __builtin_amdgcn_s_setprio(0);
-    fwd_tile_epilogue_t<WL, 2, TL, TSW, BM>(p, acc, scale, b, s0, st * BM, nt, red, cacc, cols,
-                                            soft_any, sbo);
-    if (prio1)
-      __builtin_amdgcn_s_setprio(1);
-    else
-      __builtin_amdgcn_s_setprio(0);
-  }
-}
-
-template <int TSA, int TSB, int TL>
-__global__ __launch_bounds__(512, 1) void probit_fwd16a_kernel(FwdParams p) {
-  constexpr int WL = 4, WS = 2, NW = 8, NSTAGE = 2;
-  constexpr int BM = (TSA + TSB) * 16, BN = WL * TL * 16;
-  static_assert(BM == 128, "the sample tile stays 128");
-  constexpr int STAGE = (BM + BN) * kRowB;
-  constexpr int RED = WL * BM * 6, CACC = WS * BN * 2;  // floats
-  __shared__ __attribute__((aligned(1024))) char smem[NSTAGE * STAGE + (RED + CACC + kColsT * BN) * 4];
-  float* red = reinterpret_cast<float*>(smem + NSTAGE * STAGE);
-  float* cacc = red + RED;
-  float* cols = cacc + CACC;
-
-  int g, nt;
-  decode_block(blockIdx.x, p.B * p.nSc, p.nNt, g, nt);
-  const int b = g / p.nSc, sc = g % p.nSc;
-  const int n0 = nt * BN;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wl = wid % WL;
-  const int lr = lane & 15, lg = lane >> 4;
-  const float scale = 1.0f / (*p.eps16.scale * *p.R16.scale);
-  const int nK = (p.z + kKC - 1) / kKC;
-  const int sw = (lr >> 1) & 7;
-  const int coh = (lg ^ sw) << 4, col = ((4 + lg) ^ sw) << 4;
-  const int t_begin = sc * p.tps, t_end = min(p.nSt, (sc + 1) * p.tps);
-
-  fwd_cols_stage_t<BN>(cols, p, b, n0, NW * 64);
-  for (int i = tid; i < CACC; i += NW * 64) cacc[i] = 0.0f;
-  const bool soft_any = fwd_tile_soft<BN>(p, b, n0, NW * 64);
-  const bool dmaw = wid >= NW / 2;  // the TSB half streams the stages
-  Fwd16Dma<BM, BN, NW / 2> dma;
-  dma.init(p, t_begin, b, n0, wid % (NW / 2), lane);
-  if (dmaw) {
-#pragma unroll
-    for (int j = 0; j < NSTAGE - 1; ++j) dma.issue(p, smem + j * STAGE, t_end, nK, b);
-  }
-  // the second half of the waves loses every age arbitration on its SIMD;
-  // static priority (MI355X_MICROARCH.md, two waves per SIMD, item 4)
-  const bool prio1 = dmaw;
-  if (prio1) __builtin_amdgcn_s_setprio(1);
-  if (wid < NW / 2)
-    fwd16a_tiles<TSA, true, TSA, TSB, TL>(p, smem, red, cacc, cols, dma, false, b, nt, t_begin, t_end,
-                                      nK, soft_any, wl, 0, lr, coh, col, scale, prio1);
-  else
-    fwd16a_tiles<TSB, false, TSA, TSB, TL>(p, smem, red, cacc, cols, dma, true, b, nt, t_begin, t_end,
-                                       nK, soft_any, wl, TSA, lr, coh, col, scale, prio1);
-  fwd16t_colpart<WS, BN>(p, cacc, b, sc, n0, NW * 64);
-}
-
-// ------------- 3xf16, 256 labels x 256 samples (probit_fwd16b, the C4/C5 tile)
-// probit_fwd16a with twice the samples per tile (dispatched for L > 128 and
-// S >= 256; C4 forward 13.6 -> 12.5 ms, round 6): the stage image streams
-// (256 + 256) rows for 256 x 256 x 32 products instead of (256 + 128) for
-// 256 x 128 x 32 (a third fewer operand bytes per product), and each wave's
-// fragment reads cover 64 x TS*16 products.  The accumulators (TL x TSW
-// blocks) leave room for all R fragments of a stage but not all eps ones, so
-// the eps fragments of one 16-sample block are read right before its
-// products (one block ahead).  The row-statistics exchange (red, 24 KB)
-// lives in the stage image the tile's last K stage was read from; the
-// epilogue runs in parts of kFwdBPart sample blocks.
-//
-// Fwd16Dma for S >= BM (no row clamp): the pieces of one operand image are
-// 32 rows apart, and (r >> 1) & 7 repeats every 16 rows, so every piece of an
-// image has the same per-lane offset from its (wave-uniform) row base -- two
-// offset VGPRs instead of JA + JB.
-template <int BM, int BN, int NW>
-struct Fwd16DmaLin {
-  static constexpr int GA = BM / 8, GB = BN / 8;
-  static constexpr int JA = GA / NW, JB = GB / NW;
-  static_assert(GA % NW == 0 && GB % NW == 0, "pieces split evenly over the DMA waves");
-  const char* a_base;  // eps rows of the current tile, this wave's first piece
-  const char* b_base;  // R rows of the label tile, this wave's first piece
-  int64_t a_step, b_step;  // bytes between a wave's consecutive pieces (NW * 8 rows)
-  uint32_t offa, offb;
-  int tile, kc, issued, wid;
-
-  MPV_DEV void init(const FwdParams& p, int t0, int b, int n0, int wid_, int lane) {
-    wid = wid_;
-    const int64_t lda = p.eps16.ld, ldb = p.R16.ld;
-    const int prow = lane >> 3, u_lds = lane & 7;
-    a_step = (int64_t)NW * 8 * lda * 2;
-    b_step = (int64_t)NW * 8 * ldb * 2;
-    b_base = reinterpret_cast<const char*>(p.R16.data + ((int64_t)n0 + wid * 8) * ldb);
-    offa = (uint32_t)(prow * lda * 2) + (uint32_t)((u_lds ^ (((wid * 8 + prow) >> 1) & 7)) * 16);
-    offb = (uint32_t)(prow * ldb * 2) + (uint32_t)((u_lds ^ (((wid * 8 + prow) >> 1) & 7)) * 16);
-    tile = t0;
-    kc = 0;
-    issued = 0;
-    set_tile(p, b);
-  }
-  MPV_DEV void set_tile(const FwdParams& p, int b) {
-    const int64_t o = ((int64_t)b * p.S + fwd_tile_s0<BM>(tile, p.S) + wid * 8) * p.eps16.ld;
-    a_base = reinterpret_cast<const char*>(p.eps16.data + o);
-  }
-  MPV_DEV void issue(const FwdParams& p, char* dst, int tile_end, int nK, int b) {
-    if (tile >= tile_end) return;
-    const int kb = kc * kRowB;
-#pragma unroll
-    for (int j = 0; j < JA; ++j)
-      lds_dma16(a_base + kb + j * a_step, offa, lds_addr(dst + (wid + j * NW) * 1024));
-#pragma unroll
-    for (int j = 0; j < JB; ++j)
-      lds_dma16(b_base + kb + j * b_step, offb, lds_addr(dst + BM * kRowB + (wid + j * NW) * 1024));
-    ++issued;
-    if (++kc == nK) {
-      kc = 0;
-      if (++tile < tile_end) set_tile(p, b);
-    }
-  }
-};
-
-template <int TSW, int TL>
-MPV_DEV void fwd16b_stage(f32x4 (&acc)[TL][TSW], const char* base, int wl, int sbo, int lr, int coh,
-                          int col) {
-  constexpr int BM = 256;
+// One K stage of the wave's TL x TSW blocks, eps fragments one 16-sample
+// block ahead of their products (Tile::AHEAD): the same products per
+// accumulator in the same order as fwd16t_mfma.
+template <class Tile, int TSW>
+MPV_DEV void fwd16_stage_ahead(f32x4 (&acc)[Tile::TL][TSW], const char* base, int wl, int sbo, int lr,
+                               int coh, int col) {
+  constexpr int TL = Tile::TL, BM = Tile::BM;
   s16x8 rh[TL], rl[TL];
 #pragma unroll
   for (int m = 0; m < TL; ++m) {
@@ -1170,109 +1120,109 @@ MPV_DEV void fwd16b_stage(f32x4 (&acc)[TL][TSW], const char* base, int wl, int s
   }
 }
 
-template <int PART, int NP, int TL, int TSW, int BM>
-MPV_DEV void fwd16b_epilogue_parts(const FwdParams& p, f32x4 (&acc)[TL][TSW], float scale, int b, int s0,
-                                   int s_own, int nt, float* red, float* cacc, const float* cols,
-                                   bool soft_any, int sbo) {
-  constexpr int H0 = TSW / NP, H = PART + 1 < NP ? H0 : TSW - (NP - 1) * H0;  // the last takes the rest
-  static_assert(H0 >= 1, "a block per part at least");
-  f32x4 a[TL][H];
+// A tile's epilogue: whole, or in parts of Tile::EPI_PART sample blocks (the
+// row statistics of one part in registers at a time).
+template <class Tile, int TSW, int PART = 0>
+MPV_DEV void fwd16_epilogue(const FwdParams& p, const Fwd16Ctx c, f32x4 (&acc)[Tile::TL][TSW], int s0,
+                            int s_own, int sbo, float* red) {
+  constexpr int NP = (Tile::EPI_PART > 0 && TSW / Tile::EPI_PART > 0) ? TSW / Tile::EPI_PART : 1;
+  if constexpr (NP == 1) {
+    fwd_tile_epilogue_t<Tile, TSW>(p, c, acc, s0, s_own, sbo, red);
+  } else {
+    constexpr int H0 = TSW / NP, H = PART + 1 < NP ? H0 : TSW - (NP - 1) * H0;  // the last takes the rest
+    f32x4 a[Tile::TL][H];
 #pragma unroll
-  for (int m = 0; m < TL; ++m)
+    for (int m = 0; m < Tile::TL; ++m)
 #pragma unroll
-    for (int n = 0; n < H; ++n) a[m][n] = acc[m][PART * H0 + n];
-  fwd_tile_epilogue_t<4, 2, TL, H, BM, PART == 0, kFwdBEpi, PART == NP - 1, kFwdBCQ>(
-      p, a, scale, b, s0, s_own, nt, red, cacc, cols, soft_any, sbo + PART * H0);
-  if constexpr (PART + 1 < NP)
-    fwd16b_epilogue_parts<PART + 1, NP, TL, TSW, BM>(p, acc, scale, b, s0, s_own, nt, red, cacc, cols,
-                                                     soft_any, sbo);
+      for (int n = 0; n < H; ++n) a[m][n] = acc[m][PART * H0 + n];
+    fwd_tile_epilogue_t<Tile, H, PART == 0, PART == NP - 1>(p, c, a, s0, s_own, sbo + PART * H0, red);
+    if constexpr (PART + 1 < NP) fwd16_epilogue<Tile, TSW, PART + 1>(p, c, acc, s0, s_own, sbo, red);
+  }
 }
 
-template <int TSW, int TSA, int TSB, int TL>
-MPV_DEV void fwd16b_tiles(const FwdParams& p, char* smem, float* cacc, const float* cols,
-                          Fwd16DmaLin<256, TL * 64, 4>& dma, bool dmaw, int b, int nt, int t_begin,
-                          int t_end, int nK, bool soft_any, int wl, int sbo, int lr, int coh, int col,
-                          float scale, bool prio1) {
-  constexpr int BM = 256, NSTAGE = 2;
-  constexpr int STAGE = (BM + TL * 64) * kRowB;
+// The s-tiles of one wave: TSW 16-sample blocks from sbo on, of every tile
+// the workgroup owns.  red_lds: the row-statistics exchange of the tiles that
+// keep it outside the ring.
+template <class Tile, int TSW>
+MPV_DEV void fwd16_tiles(const FwdParams& p, const Fwd16Ctx c, char* smem, float* red_lds,
+                         typename Tile::Dma& dma, bool dmaw, int sbo) {
+  constexpr int TL = Tile::TL, BM = Tile::BM;
+  constexpr int STAGE = (BM + Tile::BN) * kRowB;
   int gs = 0;
-  for (int st = t_begin; st < t_end; ++st) {
+  for (int st = c.t_begin; st < c.t_end; ++st) {
     const int s0 = fwd_tile_s0<BM>(st, p.S);
     f32x4 acc[TL][TSW];
 #pragma unroll
     for (int m = 0; m < TL; ++m)
 #pragma unroll
       for (int n = 0; n < TSW; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int kc = 0; kc < nK; ++kc, ++gs) {
+    for (int kc = 0; kc < c.nK; ++kc, ++gs) {
       wait_vmcnt<0>();
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       barrier_raw();  // stage gs landed for every wave; every wave is done reading gs-1
       if (dmaw) {
-        dma.issue(p, smem + ((__builtin_amdgcn_readfirstlane(gs) + NSTAGE - 1) % NSTAGE) * STAGE,
-                  t_end, nK, b);
+        dma.issue(p, smem + ((__builtin_amdgcn_readfirstlane(gs) + kFwdRing - 1) % kFwdRing) * STAGE,
+                  c.t_end, c.nK, c.b);
       }
-      fwd16b_stage<TSW, TL>(acc, smem + (gs % NSTAGE) * STAGE, wl, sbo, lr, coh, col);
+      const char* img = smem + (gs % kFwdRing) * STAGE;
+      if constexpr (Tile::AHEAD) {
+        fwd16_stage_ahead<Tile, TSW>(acc, img, c.wl, sbo, c.lr, c.coh, c.col);
+      } else {
+        FragT<TL, TSW> f;
+        fwd16t_read<TL, TSW, BM>(f, img, c.wl, sbo, c.lr, c.coh, c.col);
+        fwd16t_mfma<TL, TSW>(acc, f);
+      }
     }
     __builtin_amdgcn_s_setprio(0);
-    // the image of stage gs-1 (read last) is free until the next tile's first
-    // barrier; stage gs streams into the other one meanwhile
-    float* red = reinterpret_cast<float*>(smem + ((gs + NSTAGE - 1) % NSTAGE) * STAGE);
-    // in parts of kFwdBPart sample blocks (the row statistics of
-    // one part in registers at a time)
-    fwd16b_epilogue_parts<0, (TSW / kFwdBPart > 0 ? TSW / kFwdBPart : 1), TL, TSW, BM>(p, acc, scale, b, s0, st * BM, nt, red, cacc,
-                                                      cols, soft_any, sbo);
-    if (prio1)
+    // in the ring: the image of stage gs-1 (read last) is free until the next
+    // tile's first barrier; stage gs streams into the other one meanwhile
+    float* red = Tile::RED_IN_RING
+                     ? reinterpret_cast<float*>(smem + ((gs + kFwdRing - 1) % kFwdRing) * STAGE)
+                     : red_lds;
+    fwd16_epilogue<Tile, TSW>(p, c, acc, s0, st * BM, sbo, red);
+    // back to the K-loop priorities
+    if (dmaw)
       __builtin_amdgcn_s_setprio(1);
     else
       __builtin_amdgcn_s_setprio(0);
   }
 }
 
-template <int TSA, int TSB, int TL>
-__global__ __launch_bounds__(512, 1) void probit_fwd16b_kernel(FwdParams p) {
-  constexpr int WL = 4, WS = 2, NW = 8, NSTAGE = 2;
-  constexpr int BM = (TSA + TSB) * 16, BN = WL * TL * 16;
-  static_assert(BM == 256, "the sample tile is 256");
+// Every transposed 3xf16 tile (the descriptors above): 8 waves, 2-stage
+// LDS-DMA ring, one workgroup per CU.
+template <class Tile>
+__global__ __launch_bounds__(kFwd16Threads, 1) void probit_fwd16_kernel(FwdParams p) {
+  constexpr int WL = Tile::WL, WS = Tile::WS, TSA = Tile::TSA, TSB = Tile::TSB;
+  constexpr int BM = Tile::BM, BN = Tile::BN;
+  static_assert(WL * WS * 64 == kFwd16Threads && BN == WL * Tile::TL * 16 &&
+                    BM == WS / 2 * (TSA + TSB) * 16 && (TSA == TSB || WS == 2),
+                "the descriptor's geometry");
   constexpr int STAGE = (BM + BN) * kRowB;
-  static_assert(WL * BM * 6 * 4 <= STAGE, "red fits one stage image");
-  constexpr int CACC = WS * kFwdBCQ * BN * 2;  // floats
-  __shared__ __attribute__((aligned(1024))) char smem[NSTAGE * STAGE + (CACC + kColsT * BN) * 4];
-  float* cacc = reinterpret_cast<float*>(smem + NSTAGE * STAGE);
-  float* cols = cacc + CACC;
+  constexpr int RED = Tile::RED_IN_RING ? 0 : WL * BM * 6, CACC = WS * Tile::CQ * BN * 2;  // floats
+  static_assert(!Tile::RED_IN_RING || WL * BM * 6 * 4 <= STAGE, "red fits one stage image");
+  constexpr int LDS = kFwdRing * STAGE + (RED + CACC + kColsT * BN) * 4;
+  __shared__ __attribute__((aligned(1024))) char smem[LDS > Tile::LDS_MIN ? LDS : Tile::LDS_MIN];
+  float* red = reinterpret_cast<float*>(smem + kFwdRing * STAGE);
+  float* cacc = red + RED;
 
-  int g, nt;
-  decode_block(blockIdx.x, p.B * p.nSc, p.nNt, g, nt);
-  const int b = g / p.nSc, sc = g % p.nSc;
-  const int n0 = nt * BN;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wl = wid % WL;
-  const int lr = lane & 15, lg = lane >> 4;
-  const float scale = 1.0f / (*p.eps16.scale * *p.R16.scale);
-  const int nK = (p.z + kKC - 1) / kKC;
-  const int sw = (lr >> 1) & 7;
-  const int coh = (lg ^ sw) << 4, col = ((4 + lg) ^ sw) << 4;
-  const int t_begin = sc * p.tps, t_end = min(p.nSt, (sc + 1) * p.tps);
-
-  fwd_cols_stage_t<BN>(cols, p, b, n0, NW * 64);
-  for (int i = tid; i < CACC; i += NW * 64) cacc[i] = 0.0f;
-  const bool soft_any = fwd_tile_soft<BN>(p, b, n0, NW * 64);
-  const bool dmaw = wid >= NW / 2;  // the TSB half streams the stages
-  Fwd16DmaLin<BM, BN, NW / 2> dma;
-  dma.init(p, t_begin, b, n0, wid % (NW / 2), lane);
+  const Fwd16Ctx c = fwd16_ctx<Tile>(p, cacc, cacc + CACC);
+  const bool dmaw = c.wid >= 4;  // the second (TSB) half streams the stages
+  typename Tile::Dma dma;
+  dma.init(p, c.t_begin, c.b, c.n0, c.wid % 4, threadIdx.x & 63);
   if (dmaw) {
 #pragma unroll
-    for (int j = 0; j < NSTAGE - 1; ++j) dma.issue(p, smem + j * STAGE, t_end, nK, b);
+    for (int j = 0; j < kFwdRing - 1; ++j) dma.issue(p, smem + j * STAGE, c.t_end, c.nK, c.b);
   }
-  const bool prio1 = dmaw;
-  if (prio1) __builtin_amdgcn_s_setprio(1);
-  if (wid < NW / 2)
-    fwd16b_tiles<TSA, TSA, TSB, TL>(p, smem, cacc, cols, dma, false, b, nt, t_begin, t_end, nK,
-                                    soft_any, wl, 0, lr, coh, col, scale, prio1);
+  // the second half of the waves loses every age arbitration on its SIMD;
+  // static priority (MI355X_MICROARCH.md, two waves per SIMD, item 4)
+  if (dmaw) __builtin_amdgcn_s_setprio(1);
+  if constexpr (TSA == TSB)
+    fwd16_tiles<Tile, TSA>(p, c, smem, red, dma, dmaw, c.ws * TSA);
+  else if (c.wid < 4)
+    fwd16_tiles<Tile, TSA>(p, c, smem, red, dma, false, 0);
   else
-    fwd16b_tiles<TSB, TSA, TSB, TL>(p, smem, cacc, cols, dma, true, b, nt, t_begin, t_end, nK,
-                                    soft_any, wl, TSA, lr, coh, col, scale, prio1);
-  fwd16t_colpart<WS, BN, kFwdBCQ>(p, cacc, b, sc, n0, NW * 64);
+    fwd16_tiles<Tile, TSB>(p, c, smem, red, dma, true, TSA);
+  fwd16t_colpart<WS * Tile::CQ, BN>(p, cacc, c.b, c.sc, c.n0);
 }
 
 // The six scalars of compute_loss (mpvae.py:147-148 KL, :188-190 nll, :122
@@ -1512,32 +1462,54 @@ __global__ __launch_bounds__(kFinalThreads) void finalize_kernel(mpv_final_args 
 }
 
 // ---------------------------------------------------------------- host side
-struct FwdPlan {
-  int cfg;  // tile configuration, see launch_fwd
-  int BM, BN, nNt, nSt, nSc, tps;
-  size_t rowpart_bytes, colpart_bytes;
+// A tile as the host sees it: its geometry and the kernel that computes it.
+struct FwdTile {
+  int BM, BN, threads;
+  void (*kernel)(FwdParams);
 };
+template <class Tile>
+static FwdTile fwd16_tile() {
+  return {Tile::BM, Tile::BN, kFwd16Threads, probit_fwd16_kernel<Tile>};
+}
+template <int WM, int WN, int TM, int TN>
+static FwdTile fwd32_tile() {
+  return {WM * TM * 16, WN * TN * 16, WM * WN * 64, probit_fwd_kernel<WM, WN, TM, TN>};
+}
 
-static FwdPlan plan_fwd(const mpv_shape* s, int gemm) {
-  FwdPlan pl;
-  // tile configurations: 0 = 48 labels (L <= 48), 1 = 96 labels (fp32 mode,
-  // L <= 96; 3xf16: the transposed 96 x 128 tile), 2 = 128 labels (transposed
-  // 3xf16 tile, or the fp32 64 x 64 waves), 3 = 256 labels (3xf16, L > 128).
-  // (Round 2 measured a 3xf16 96-label tile with MFMA-layout accumulators
-  // slower at C3 than the 128-label transposed tile; the transposed 96-label
-  // tile is the one used now.)
-  const bool f16 = gemm == MPV_GEMM_F16X3;
-  pl.cfg = s->L <= 48 ? 0 : (s->L <= 96 ? 1 : ((f16 && s->L > 128) ? 3 : 2));
+// 48 labels (L <= 48), 96 labels (L <= 96), 128 labels (the transposed 3xf16
+// tile, or the fp32 64 x 64 waves), 256 labels (3xf16, L > 128).
+// (Round 2 measured a 3xf16 96-label tile with MFMA-layout accumulators
+// slower at C3 than the 128-label transposed tile; the transposed 96-label
+// tile is the one used now.)
+static FwdTile pick_fwd_tile(const mpv_shape* s, int gemm) {
+  const int64_t L = s->L;
+  if (gemm != MPV_GEMM_F16X3)
+    return L <= 48 ? fwd32_tile<4, 1, 2, 3>()
+                   : (L <= 96 ? fwd32_tile<4, 1, 2, 6>() : fwd32_tile<2, 2, 4, 4>());
+  if (L <= 48) return fwd16_tile<Fwd16tTile48x256>();
+  if (L <= 96) return fwd16_tile<Fwd16tTile96x128>();
+  if (L <= 128) return fwd16_tile<Fwd16aTile128x128>();
   // (the 256 x 256 tile streams whole tiles: S >= 256, Fwd16DmaLin.
   // MPVAE_FWD_TILE=256x128 selects round 5's tile instead: a diagnostic for
   // the tests that compare the two, not a tuning knob)
   const char* tile_env = std::getenv("MPVAE_FWD_TILE");
   const bool tile128 = tile_env != nullptr && std::strcmp(tile_env, "256x128") == 0;
-  pl.BM = (f16 && pl.cfg == 0) ? kFwd48BM
-                               : ((f16 && pl.cfg == 3 && !tile128 && s->S_local >= 256) ? 256 : 128);
-  pl.BN = pl.cfg == 0 ? 48 : (pl.cfg == 1 ? 96 : (pl.cfg == 2 ? 128 : 256));
-  pl.nNt = (int)cdiv(s->L, pl.BN);
-  pl.nSt = (int)cdiv(s->S_local, pl.BM);
+  return (tile128 || s->S_local < 256) ? fwd16_tile<Fwd16aTile256x128>()
+                                       : fwd16_tile<Fwd16bTile256x256>();
+}
+
+struct FwdPlan {
+  FwdTile tile;
+  int nNt, nSt, nSc, tps;
+  size_t rowpart_bytes, colpart_bytes;
+};
+
+static FwdPlan plan_fwd(const mpv_shape* s, int gemm) {
+  FwdPlan pl;
+  pl.tile = pick_fwd_tile(s, gemm);
+  const bool f16 = gemm == MPV_GEMM_F16X3;
+  pl.nNt = (int)cdiv(s->L, pl.tile.BN);
+  pl.nSt = (int)cdiv(s->S_local, pl.tile.BM);
   // 3xf16: s-chunks until the grid is one round of resident workgroups (one
   // per CU: every 3xf16 tile is 8 waves); longer runs per
   // workgroup amortize its prologue (C3 step 0.534 -> 0.510 ms against a
@@ -1553,47 +1525,8 @@ static FwdPlan plan_fwd(const mpv_shape* s, int gemm) {
   return pl;
 }
 
-static void launch_fwd(const FwdPlan& pl, int gemm, dim3 grid, hipStream_t st, const FwdParams& p) {
-  if (gemm == MPV_GEMM_F32) {
-    switch (pl.cfg) {
-      case 0:
-        MPV_LAUNCH("probit_fwd", (probit_fwd_kernel<4, 1, 2, 3>), grid, dim3(256), 0, st, p);
-        break;
-      case 1:
-        MPV_LAUNCH("probit_fwd", (probit_fwd_kernel<4, 1, 2, 6>), grid, dim3(256), 0, st, p);
-        break;
-      default:
-        MPV_LAUNCH("probit_fwd", (probit_fwd_kernel<2, 2, 4, 4>), grid, dim3(256), 0, st, p);
-        break;
-    }
-  } else {
-    switch (pl.cfg) {
-      case 0:  // 48 labels x kFwd48BM samples, transposed, 8 waves, one workgroup per CU
-        MPV_LAUNCH("probit_fwd", (probit_fwd16t_kernel<1, 8, 3, kFwd48BM / 128, 2, 82 * 1024>), grid,
-                   dim3(512), 0, st, p);
-        break;
-      case 3:  // 256 labels x 128 samples, 8 waves, asymmetric 80 / 48 sample split
-        if (pl.BM == 256)
-          MPV_LAUNCH("probit_fwd", (probit_fwd16b_kernel<kFwdBA, 16 - kFwdBA, 4>), grid, dim3(512), 0, st, p);
-        else
-          MPV_LAUNCH("probit_fwd", (probit_fwd16a_kernel<5, 3, 4>), grid, dim3(512), 0, st, p);
-        break;
-      case 1:  // 96 labels x 128 samples (48 < L <= 96), 8 waves of 48 x 32, even split
-        MPV_LAUNCH("probit_fwd", (probit_fwd16t_kernel<2, 4, 3, 2, 2>), grid, dim3(512), 0, st, p);
-        break;
-      default:
-        // 128 labels x 128 samples (96 < L <= 128), 8 waves, asymmetric 80 / 48
-        // sample split (C3 before the 96-label tile: forward 0.187 -> 0.181 ms
-        // against the even 64 / 64 split).  A
-        // 4-wave version of this tile (64 x 64 per wave, two workgroups per CU)
-        // ran 0.031 ms faster at C3 but was not repeatable: 10-13 % of its
-        // launches at C3 differed in one label-branch row statistic of a
-        // 16-sample block (never with one workgroup per CU, the same code padded
-        // to 81 KB of LDS; DESIGN.md section 4, tools/repeat_probe.py)
-        MPV_LAUNCH("probit_fwd", (probit_fwd16a_kernel<5, 3, 2>), grid, dim3(512), 0, st, p);
-        break;
-    }
-  }
+static void launch_fwd(const FwdPlan& pl, dim3 grid, hipStream_t st, const FwdParams& p) {
+  MPV_LAUNCH("probit_fwd", pl.tile.kernel, grid, dim3(pl.tile.threads), 0, st, p);
 }
 
 static int check_split_operand(const mpv_split16& o, int64_t rows, int64_t ld_min,
@@ -1659,11 +1592,11 @@ static int run_fwd(const mpv_shape* shape, const mpv_fwd_args* a, void* stream) 
     MPV_REQUIRE(a->R32 && a->eps, "MPV_GEMM_F32 needs R32 and eps");
   } else {
     const int64_t ldk = 2 * cdiv(shape->z, kKC) * kKC;  // K slices the main loop reads
-    if (int rc = check_split_operand(a->R16, (int64_t)pl.nNt * pl.BN, ldk, "R16")) return rc;
+    if (int rc = check_split_operand(a->R16, (int64_t)pl.nNt * pl.tile.BN, ldk, "R16")) return rc;
     if (int rc = check_split_operand(a->eps16, shape->S_local * shape->B, ldk, "eps16")) return rc;
     // the DMA issue keeps per-lane byte offsets within one s/l tile in 32 bits
-    MPV_REQUIRE((int64_t)pl.BM * a->eps16.ld * 2 < (int64_t(1) << 32) &&
-                    (int64_t)pl.BN * a->R16.ld * 2 < (int64_t(1) << 32),
+    MPV_REQUIRE((int64_t)pl.tile.BM * a->eps16.ld * 2 < (int64_t(1) << 32) &&
+                    (int64_t)pl.tile.BN * a->R16.ld * 2 < (int64_t(1) << 32),
                 "ld too large for the f16x3 tile offsets");
   }
   const size_t need = pl.rowpart_bytes + pl.colpart_bytes;
@@ -1693,7 +1626,7 @@ static int run_fwd(const mpv_shape* shape, const mpv_fwd_args* a, void* stream) 
   p.nSt = pl.nSt;
   const int64_t blocks = (int64_t)shape->B * pl.nSc * pl.nNt;
   MPV_REQUIRE(blocks < (int64_t(1) << 31), "grid too large");
-  launch_fwd(pl, a->gemm, dim3((unsigned)blocks), st, p);
+  launch_fwd(pl, dim3((unsigned)blocks), st, p);
   if (int rc = check_launch("probit_fwd")) return rc;
   // few s-chunks: fwd_combine sums the column partials too (one launch less);
   // many (small B, long S): the slab-sum kernel's split reduction

@@ -930,8 +930,8 @@ def test_forward_statistics_bitwise_repeatable(B, S, L, z):
 @pytest.mark.parametrize("B,S,L,z", [(8, 4096, 1024, 1024), (3, 700, 300, 200), (2, 256, 260, 64)],
                          ids=["c4dims", "ragged", "s256"])
 def test_256x256_tile_equals_256x128_tile(B, S, L, z, monkeypatch):
-    """The shipped 256-label x 256-sample forward tile (probit_fwd16b, S >= 256)
-    and round 5's 256 x 128 tile (probit_fwd16a, still dispatched for S < 256,
+    """The shipped 256-label x 256-sample forward tile (Fwd16bTile256x256, S >= 256)
+    and round 5's 256 x 128 tile (Fwd16aTile256x128, still dispatched for S < 256,
     where the probit sweep of test_gpu_probit_ulp.py runs) compute every t
     with the same MFMA sequence and the same epilogue code, so T, the per-sample
     statistics and the batch statistics agree bit for bit; only the column
