@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MPV_ABI_VERSION 11 /* 4: device-memory Philox keys (mpv_noise_philox*_dev);
+#define MPV_ABI_VERSION 12 /* 4: device-memory Philox keys (mpv_noise_philox*_dev);
                               5: T rows padded to roundup(L, 4) floats;
                               6: mpv_linear (the VAE's Linear layers); mpv_bwd_args
                                  dR64 and kl;
@@ -49,7 +49,9 @@ extern "C" {
                                  the live slots of gscal are read (mpv_kl_bwd_args
                                  .live); mpv_noise_philox_f16_split;
                                  mpv_final_args.seed_advance
-                             11: mpv_curve_metrics (validation AUC / AUPR / FDR) */
+                             11: mpv_curve_metrics (validation AUC / AUPR / FDR)
+                             12: mpv_threshold_sweep (the threshold metrics of
+                                 up to 64 thresholds from one read of the split) */
 
 enum mpv_status { MPV_OK = 0, MPV_EINVAL = 1, MPV_ELAUNCH = 2 };
 enum mpv_dtype { MPV_F32 = 0, MPV_F64 = 1 };
@@ -431,7 +433,8 @@ int mpv_adam_finish(const mpv_adam_finish_args* args, void* stream);
  * bwd_elem, dR_gemm, sum_slabs, convert, bstat_combine, reparam_fwd,
  * reparam_bwd, kl_bwd, linear, adam, adam_finish, label_weights, fair_fwd,
  * fair_bwd, metrics, curve_keys, curve_sort (the LDS chunk sort), curve_merge
- * (the merge passes), curve_pass, curve_agg.  Query synchronises the recorded events. */
+ * (the merge passes), curve_pass, curve_agg, metric_sweep (every launch of
+ * mpv_threshold_sweep).  Query synchronises the recorded events. */
 int mpv_timing_enable(int on);
 int mpv_timing_reset(void);
 int mpv_timing_query(const char* kernel, int64_t* launches, double* total_ms);
@@ -521,6 +524,30 @@ typedef struct mpv_curve_args {
 size_t mpv_curves_workspace_bytes(int64_t N, int64_t L, int64_t chunk);
 int mpv_curve_metrics(const mpv_curve_args* args, void* workspace, size_t workspace_bytes,
                       void* stream);
+
+/* ---- Threshold sweep: the selection loop of validate_mpvae
+ * (fairsoft_train.py:400-416; sweep.hip) -------------------------------------
+ * Row j of out = what mpv_train_metrics gives at thr[j]: [ACC, HA, ebF1, miF1,
+ * maF1, p@1, p@3, p@5], for every threshold from one read of pred / target.
+ * A prediction is 1 iff !(p < thr) in fp32.  The thresholds need no order and
+ * may repeat: the rows come in the caller's order.  Every count is an integer
+ * (exact for N < 2^31); ACC, miF1 and p@1 equal mpv_train_metrics bit for bit
+ * wherever its fp32 counts are exact, the others differ from it by the order
+ * of fp64 additions only.  Fixed-order sums: two calls give the same bits. */
+#define MPV_MAX_THRESHOLDS 64
+typedef struct mpv_sweep_args {
+  const float* pred;    /* (N, L) */
+  const float* target;  /* (N, L) exact 0 / 1 */
+  int64_t N, L;         /* 0 < N < 2^31, 0 < L <= 4096 (as mpv_curve_args) */
+  int64_t n_thr;        /* 1 .. MPV_MAX_THRESHOLDS */
+  float thr[MPV_MAX_THRESHOLDS];
+  double* out;          /* (n_thr, 8) */
+} mpv_sweep_args;
+
+/* 0 for a bad shape or threshold count. */
+size_t mpv_sweep_workspace_bytes(int64_t N, int64_t L, int64_t n_thr);
+int mpv_threshold_sweep(const mpv_sweep_args* args, void* workspace, size_t workspace_bytes,
+                        void* stream);
 
 #ifdef __cplusplus
 }

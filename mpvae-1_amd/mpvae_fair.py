@@ -33,6 +33,9 @@ The validation form, ``compute_metrics(..., all_metrics=True)`` and
 ``best_threshold_metrics`` (the threshold sweep of validate_mpvae,
 fairsoft_train.py:400-416), runs in csrc/curves.hip: one descending sort per
 label of the whole validation split, then AUC / AUPR / FDR from per-run totals.
+The sweep's threshold metrics come from csrc/sweep.hip
+(``threshold_sweep_metrics``: every threshold from one read of the split;
+``best_thresholds`` reads the winning thresholds off its table).
 Differences from the reference:
 * ``allAUC`` / ``allAUPR`` / ``allFDR`` always have length L; a label the
   metric is undefined for (AUC of a one-class label) holds NaN where the
@@ -328,21 +331,66 @@ def compute_metrics(predictions, targets, threshold, all_metrics=False, chunk=0)
     return res
 
 
+def threshold_sweep_metrics(predictions, targets, thresholds=THRESHOLDS):
+    """The threshold metrics of ``compute_metrics(predictions, targets, thr)``
+    at every ``thr`` of ``thresholds`` from one read of the split
+    (mpv_threshold_sweep, csrc/sweep.hip): an (n_thr, 8) fp64 device tensor,
+    row j for ``thresholds[j]``, columns in METRIC_KEYS order.  The thresholds
+    need no order and may repeat; more than 64 run in slices of 64.  ACC, miF1
+    and p_at_1 equal the per-threshold call bit for bit, the others differ
+    from it by the order of fp64 additions only.  No host sync."""
+    thresholds = [float(x) for x in thresholds]
+    if not thresholds:
+        raise ValueError("threshold_sweep_metrics needs at least one threshold")
+    H.require_gpu(predictions, targets)
+    p = predictions.detach().contiguous().float()
+    t = targets.detach().contiguous().float()
+    N, L = p.shape
+    lib, st = H.load_library(), H.stream_of(p.device)
+    out = torch.empty((len(thresholds), 8), dtype=torch.float64, device=p.device)
+    for j0 in range(0, len(thresholds), H.MAX_THRESHOLDS):
+        part = thresholds[j0:j0 + H.MAX_THRESHOLDS]
+        nbytes = lib.mpv_sweep_workspace_bytes(N, L, len(part))
+        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=p.device)
+        a = H.SweepArgs(H.ptr(p), H.ptr(t), N, L, len(part),
+                        (ctypes.c_float * H.MAX_THRESHOLDS)(*part), H.ptr(out[j0]))
+        H.check(lib.mpv_threshold_sweep(ctypes.byref(a), H.ptr(ws), nbytes, st),
+                "mpv_threshold_sweep")
+    return out
+
+
+def best_thresholds(table, thresholds):
+    """For each of the eight METRIC_KEYS the first threshold at which the
+    metric attains its maximum over the rows of ``table`` (the result of
+    ``threshold_sweep_metrics`` for ``thresholds``), as 0-d fp64 tensors on the
+    table's device; NaN where the column holds a NaN, in line with ``amax``.
+    torch ops on the small table only: no host sync."""
+    thr = torch.as_tensor([float(x) for x in thresholds], dtype=torch.float64, device=table.device)
+    if table.dim() != 2 or table.shape[0] != thr.numel() or table.shape[1] != len(METRIC_KEYS):
+        raise ValueError(f"table {tuple(table.shape)} is not ({thr.numel()}, {len(METRIC_KEYS)})")
+    best = table.amax(0, keepdim=True)  # NaN where the column holds one
+    hit = (table == best).to(torch.uint8)  # all False in a NaN column
+    first = hit.argmax(0)  # the first maximal element
+    picked = torch.where(torch.isnan(best[0]), torch.full_like(best[0], float("nan")), thr[first])
+    return {k: picked[i] for i, k in enumerate(METRIC_KEYS)}
+
+
 def best_threshold_metrics(predictions, targets, thresholds=THRESHOLDS):
     """The selection loop of validate_mpvae (fairsoft_train.py:400-416) on the
     device: the METRICS of ``compute_metrics(..., thr, all_metrics=True)``
     reduced over ``thresholds``, the maximum of each, the minimum for the FDR
     entries.  The curve metrics (the FDR entries among them) do not depend on
     the threshold, so they are computed once and are their own maximum and
-    minimum; the threshold metrics take one mpv_train_metrics call per
-    threshold and their maximum is reduced on the device.
+    minimum; the threshold metrics come from ``threshold_sweep_metrics`` (one
+    pass over the split for all thresholds) and their maximum is reduced on
+    the device.
     Returns the 14 METRICS as 0-d fp64 device tensors; a NaN at any threshold
     propagates (module docstring).  No host sync."""
     H.require_gpu(predictions, targets)
     p = predictions.detach().contiguous().float()
     t = targets.detach().contiguous().float()
     curves = curve_metrics(p, t)
-    per_thr = torch.stack([_train_metrics(p, t, thr) for thr in thresholds])  # (n_thr, 8)
+    per_thr = threshold_sweep_metrics(p, t, thresholds)  # (n_thr, 8)
     best8 = per_thr.amax(0)  # propagates NaN; none of the eight is an FDR entry
     best = {k: best8[i] for i, k in enumerate(METRIC_KEYS)}
     return {k: best[k] if k in best else curves[k] for k in METRICS}

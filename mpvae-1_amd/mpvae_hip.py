@@ -13,7 +13,7 @@ import torch  # noqa: F401  (must precede the .so load: one HIP runtime per proc
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MPVAE_HIP_LIB", os.path.join(HERE, "libmpvae_hip.so"))
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 F32, F64 = 0, 1
 G_TOTAL, G_NLL, G_NLL_X, G_C, G_C_X, G_KL = range(6)
 
@@ -144,6 +144,15 @@ class CurveArgs(ctypes.Structure):
                 ("chunk", ctypes.c_int64), ("auc", vp), ("aupr", vp), ("fdr", vp), ("agg", vp)]
 
 
+MAX_THRESHOLDS = 64
+
+
+class SweepArgs(ctypes.Structure):
+    """mpv_sweep_args: the threshold metrics at up to 64 thresholds (sweep.hip)."""
+    _fields_ = [("pred", vp), ("target", vp), ("N", ctypes.c_int64), ("L", ctypes.c_int64),
+                ("n_thr", ctypes.c_int64), ("thr", ctypes.c_float * MAX_THRESHOLDS), ("out", vp)]
+
+
 # name -> (restype, argtypes); exactly the symbols of include/mpvae_hip.h
 SIGNATURES = {
     "mpv_abi_version": (ctypes.c_int, []),
@@ -201,6 +210,9 @@ SIGNATURES = {
     "mpv_curves_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64,
                                                      ctypes.c_int64]),
     "mpv_curve_metrics": (ctypes.c_int, [ctypes.POINTER(CurveArgs), vp, ctypes.c_size_t, vp]),
+    "mpv_sweep_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64,
+                                                    ctypes.c_int64]),
+    "mpv_threshold_sweep": (ctypes.c_int, [ctypes.POINTER(SweepArgs), vp, ctypes.c_size_t, vp]),
 }
 
 _lib = None
@@ -263,7 +275,8 @@ def require_gpu(*tensors):
 KERNELS = ["noise_philox", "split", "probit_fwd", "fwd_combine", "finalize", "bwd_coef", "bwd_elem",
            "dR_gemm", "sum_slabs", "convert", "bstat_combine", "reparam_fwd", "reparam_bwd",
            "kl_bwd", "label_weights", "fair_fwd", "fair_bwd", "metrics", "linear", "adam",
-           "adam_finish", "curve_keys", "curve_sort", "curve_merge", "curve_pass", "curve_agg"]
+           "adam_finish", "curve_keys", "curve_sort", "curve_merge", "curve_pass", "curve_agg",
+           "metric_sweep"]
 
 
 def kernel_times():
