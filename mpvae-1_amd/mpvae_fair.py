@@ -141,6 +141,8 @@ def label_weights(labels, tables):
     B, L = y.shape
     w = torch.empty((len(tables), B), dtype=torch.float64, device=y.device)
     count = torch.zeros((), dtype=torch.int32, device=y.device)
+    if B == 0:  # no row to look up: no launch with an empty grid
+        return w, count
     lib, st = H.load_library(), H.stream_of(y.device)
     for t, tab in enumerate(tables):
         if tab.L != L:
@@ -157,10 +159,10 @@ def group_ids(sensitive_feat):
     the number of distinct rows that sort before row b (lexicographically).
     No data-dependent shape and no host sync, so it can be captured in a HIP
     graph; O(B^2 n_sensitive) compares, a few microseconds at B = 512."""
-    X = sensitive_feat.reshape(sensitive_feat.shape[0], -1)
-    B = X.shape[0]
-    if B == 0:
-        return torch.zeros(0, dtype=torch.int32, device=X.device)
+    B = sensitive_feat.shape[0]
+    if B == 0:  # reshape(0, -1) cannot infer the second size
+        return torch.zeros(0, dtype=torch.int32, device=sensitive_feat.device)
+    X = sensitive_feat.reshape(B, -1)
     ne = X[:, None, :] != X[None, :, :]                         # [c, b, j]
     differ = ne.any(-1)                                         # rows c, b differ
     first = ne.to(torch.uint8).argmax(-1, keepdim=True)         # first differing column
@@ -226,6 +228,22 @@ class _FairPenalty(torch.autograd.Function):
         return (gl.to(ctx.dtypes[0]), gf.to(ctx.dtypes[1])) + (None,) * 7
 
 
+class _ZeroPenalty(torch.autograd.Function):
+    """The penalty of an empty batch or of no target table: the reference
+    leaves ``fairloss = 0.`` (fairsoft_train.py:83).  A zero that is still a
+    differentiable function of both inputs, with zero gradients, and launches
+    no kernel of csrc/fairness.hip."""
+
+    @staticmethod
+    def forward(ctx, label_z, feat_z):
+        ctx.save_for_backward(label_z, feat_z)
+        return torch.zeros((), dtype=torch.float64, device=label_z.device)
+
+    @staticmethod
+    def backward(ctx, gout):
+        return tuple(torch.zeros_like(t) for t in ctx.saved_tensors)
+
+
 NORMS = {"l1": H.FAIR_L1, "l2": H.FAIR_L2}
 
 
@@ -248,8 +266,14 @@ def fairness_penalty(indiv_prob_label, indiv_prob, input_label, sensitive_feat, 
     tensor to add to total_loss (zero when no term is active), computed in fp64
     and returned in the reference's dtype (fp64 if any table holds numpy
     float64 distances, else fp32), contributed the
-    int32 count that the reference adds to contributed_reg_fair_sample."""
+    int32 count that the reference adds to contributed_reg_fair_sample.
+    An empty batch or ``tables=[]`` gives an fp64 zero with zero gradients and
+    a zero count, as the reference's ``fairloss = 0.``."""
     H.require_gpu(indiv_prob_label, indiv_prob, input_label, sensitive_feat)
+    if indiv_prob_label.shape[0] == 0 or not tables:
+        # shapes and len(tables) are host knowledge: no sync, still capturable
+        count = torch.zeros((), dtype=torch.int32, device=indiv_prob_label.device)
+        return _ZeroPenalty.apply(indiv_prob_label, indiv_prob), count
     w, count = label_weights(input_label, tables)
     gid, order, goff, G, overflow = sensitive_groups(sensitive_feat, max_groups)
     norm = NORMS.get(fairness_loss_norm, 0)

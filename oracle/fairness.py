@@ -27,14 +27,18 @@ def row_weights(labels, dist):
     return out
 
 
-def fair_penalty(label_z, feat_z, labels, sensitive, dists, norm, coeff):
+def fair_penalty(label_z, feat_z, labels, sensitive, dists, norm, coeff, return_min_d=False):
     """-> (fairloss or None when no term is active, contributed count,
-    d fairloss / d label_z, d fairloss / d feat_z)."""
+    d fairloss / d label_z, d fairloss / d feat_z); with ``return_min_d`` also
+    the (L,) minimum of |d| over every active (target, group, branch)
+    difference of means (inf when none is active): how far each label of an
+    l1 case stays from sgn's discontinuity."""
     lz, fz = np.asarray(label_z, np.float64), np.asarray(feat_z, np.float64)
     B, L = lz.shape
     groups = np.unique(sensitive, axis=0)
     gid = np.array([np.flatnonzero((groups == s).all(1))[0] for s in sensitive])
     reg, gl, gf, contributed, active = 0.0, np.zeros((B, L)), np.zeros((B, L)), 0, False
+    min_d = np.full(L, np.inf)
     for dist in dists:
         w = row_weights(labels, dist)
         contributed += int((w > 0).sum())
@@ -51,6 +55,7 @@ def fair_penalty(label_z, feat_z, labels, sensitive, dists, norm, coeff):
                     continue
                 mk = (z[mask] * w[mask, None]).sum(0) / Wk
                 d = mk - m
+                min_d = np.minimum(min_d, np.abs(d))
                 if norm == "l1":
                     reg += np.abs(d).sum()
                     fp = np.sign(d)
@@ -64,6 +69,8 @@ def fair_penalty(label_z, feat_z, labels, sensitive, dists, norm, coeff):
                 esum += fp
             g -= coeff * w[:, None] * esum[None, :] / W
     loss = coeff * reg if active else None
+    if return_min_d:
+        return loss, contributed, gl, gf, min_d
     return loss, contributed, gl, gf
 
 

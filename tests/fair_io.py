@@ -32,5 +32,7 @@ def metric_fixtures():
         z = np.load(p)
         d = {k: z[k] for k in z.files}
         d["name"] = os.path.basename(p)[8:-4]
+        # the threshold the reference was run at; fixtures without one used 0.5
+        d["threshold"] = float(d["threshold"]) if "threshold" in d else 0.5
         out.append(d)
     return out

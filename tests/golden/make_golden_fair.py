@@ -16,13 +16,16 @@ reference's own code:
     the reference leaves it a Python float), contributed_reg_fair_sample, and
     the gradients of fairloss w.r.t. indiv_prob_label and indiv_prob.
 
-Usage:  PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden_fair.py
-Writes: tests/golden/fair_*.npz, tests/golden/metrics_*.npz
+Usage:  PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden_fair.py [NAME ...]
+Writes: tests/golden/fair_*.npz, tests/golden/metrics_*.npz (with names given,
+only those cases, e.g. ``f8_one_group_l257 m4_l3``: every case draws from its
+own seeded generator, so the others need not be rewritten)
 """
 import argparse
 import importlib.util
 import json
 import os
+import sys
 import textwrap
 
 import numpy as np
@@ -110,6 +113,7 @@ def make_dists(rng, labels, n_targets, n_extra, miss_rows=0, pyfloat=False):
 
 
 def main():
+    only = set(sys.argv[1:])
     block, (a, b) = fairness_block()
     print(f"fairness block: fairsoft_train.py:{a}-{b}")
     cases = [  # name, B, L, n_sens_cols, n_targets, norm, coeff, seed, miss_rows, pyfloat
@@ -120,26 +124,45 @@ def main():
         ("f5_inactive", 8, 10, 1, 1, "l1", 1.0, 5, 8, False),
         ("f6_pyfloat_l1", 64, 24, 2, 2, "l1", 1.5, 6, 4, True),
         ("f7_pyfloat_l2", 64, 90, 2, 3, "l2", 0.8, 7, 0, True),
+        # past one 256-label workgroup of fair_fwd_kernel, with a one-label tail
+        ("f8_one_group_l257", 8, 257, 1, 2, "l1", 1.5, 8, 0, False),
+        ("f9_l257_dead_target", 13, 257, 1, 3, "l1", 0.9, 9, 0, False),
     ]
     for name, B, L, ns_, T, norm, coeff, seed, miss, pyf in cases:
+        if only and name not in only:
+            continue
         rng = np.random.default_rng(100 + seed)
         labels = (rng.random((B, L)) < 0.3).astype(np.int64)
         labels[B // 2:, :] = labels[:B - B // 2, :]  # repeated patterns
         sens = rng.integers(0, 2, (B, ns_)).astype(np.int64)
         if name == "f3_zero_group":
             sens[:8, 0] = 5  # a group whose rows (the first 8) are all absent from the dicts
+        if name == "f8_one_group_l257":
+            sens[:] = 1  # one sensitive group: every difference of means is exactly 0
+        if name == "f9_l257_dead_target":
+            sens[:, 0] = np.arange(B) % 3  # three groups
         dists, targets = make_dists(rng, labels, T, 4, miss_rows=miss if name != "f5_inactive"
                                     else B, pyfloat=pyf)
+        if name == "f9_l257_dead_target":
+            # the second target's dict misses every row of the batch (W_t = 0)
+            dists[targets[1]] = {"".join(rng.integers(0, 2, L).astype(str)):
+                                 np.float64(rng.uniform(0.05, 1.0)) for _ in range(4)}
         rec = run_fair_case(block, labels, sens, dists, targets, norm, coeff, seed, pyfloat=pyf)
-        np.savez(os.path.join(HERE, f"fair_{name}.npz"), **rec)
+        # compressed: the int64 label rows of the L = 257 cases would pass 100 KB
+        np.savez_compressed(os.path.join(HERE, f"fair_{name}.npz"), **rec)
         print(name, "active", int(rec["active"]), "fairloss", float(rec["fairloss"]),
               str(rec.get("ref_dtype", "-")),
               "contributed", int(rec["contributed"]))
 
     ev = load_evals()
     keys = ["ACC", "HA", "ebF1", "miF1", "maF1", "p_at_1", "p_at_3", "p_at_5"]
-    for name, B, L, seed, zero_rows in [("m1", 64, 20, 1, 0), ("m2_zero_rows", 48, 30, 2, 6),
-                                        ("m3_l300", 16, 300, 3, 0)]:
+    for name, B, L, seed, zero_rows, thr in [("m1", 64, 20, 1, 0, 0.5),
+                                             ("m2_zero_rows", 48, 30, 2, 6, 0.5),
+                                             ("m3_l300", 16, 300, 3, 0, 0.5),
+                                             ("m4_l3", 6, 3, 4, 0, 0.5),
+                                             ("m5_thr005_l257", 5, 257, 5, 0, 0.05)]:
+        if only and name not in only:
+            continue
         rng = np.random.default_rng(200 + seed)
         tgt = (rng.random((B, L)) < 0.25).astype(np.float32)
         tgt[0, 0], tgt[0, 1] = 1, 0
@@ -147,9 +170,13 @@ def main():
         if zero_rows:
             tgt[1:1 + zero_rows] = 0
             pred[1:1 + zero_rows] = rng.random((zero_rows, L)).astype(np.float32) * 0.4
-        m = ev.compute_metrics(pred.copy(), tgt.copy(), 0.5, all_metrics=False)
+        # no ties within a row: the reference's p@k tie order is implementation-defined
+        assert all(len(np.unique(r)) == L for r in pred), name
+        m = ev.compute_metrics(pred.copy(), tgt.copy(), thr, all_metrics=False)
         vals = np.array([float(m[k]) for k in keys], np.float64)
-        np.savez(os.path.join(HERE, f"metrics_{name}.npz"), pred=pred, target=tgt, values=vals)
+        extra = {} if thr == 0.5 else {"threshold": np.array(thr)}  # absent: 0.5
+        np.savez(os.path.join(HERE, f"metrics_{name}.npz"), pred=pred, target=tgt, values=vals,
+                 **extra)
         print(name, dict(zip(keys, np.round(vals, 6))))
 
 

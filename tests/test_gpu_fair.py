@@ -91,7 +91,7 @@ def test_label_weights_multiword_and_misses():
 @pytest.mark.parametrize("m", MET, ids=[m["name"] for m in MET])
 def test_train_metrics_match_reference(m):
     res = mf.compute_metrics(torch.from_numpy(m["pred"]).to(DEV),
-                             torch.from_numpy(m["target"]).to(DEV), 0.5)
+                             torch.from_numpy(m["target"]).to(DEV), m["threshold"])
     v = np.array([float(res[k]) for k in mf.METRIC_KEYS])
     assert np.allclose(v, m["values"], rtol=1e-6, atol=1e-7), (v, m["values"])
 

@@ -30,7 +30,7 @@ def test_fair_oracle_matches_reference(f):
 
 @pytest.mark.parametrize("m", MET, ids=[m["name"] for m in MET])
 def test_metrics_oracle_matches_reference(m):
-    v = of.train_metrics(m["pred"], m["target"], 0.5)
+    v = of.train_metrics(m["pred"], m["target"], m["threshold"])
     assert np.allclose(v, m["values"], rtol=1e-6, atol=1e-7), (v, m["values"])
 
 

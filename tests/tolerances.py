@@ -89,6 +89,36 @@ LINEAR_RTOL = 2e-6
 # Measured <= 9.3e-7 (outputs and all parameter gradients).
 LINEAR_VAE_RTOL = 4e-6
 
+# csrc/fairness.hip at its edges against oracle/fairness.py
+# (tests/test_gpu_fair_edges.py; per-case figures, the oracle's own s among
+# them, in profiles/fair_edges_errs.jsonl).
+# The penalty: fp64 on both sides, a few hundred additions in another order
+# (the bound of test_gpu_fair.py's small cases).  Measured <= 4.7e-16.
+FAIR_LOSS_RTOL = 1e-12
+# A loss returned as fp32 (tables of Python floats) is that fp64 value rounded
+# once to nearest: half an fp32 ulp.  Measured 4.0e-8.
+FAIR_LOSS_F32_RTOL = 2.0 ** -24 + FAIR_LOSS_RTOL
+# ACC, HA and p@k are ratios of exact integer counts, summed over the B rows
+# in fp64 on both sides.  Measured: 0 in all 105 cases.
+METRIC_COUNT_ULP = 2.0 ** -52          # times B
+# ebF1, miF1, maF1: the reference divides in fp32 there (as test_gpu_fair.py).
+# Measured <= 4.2e-8 absolute.
+METRIC_F1_RTOL, METRIC_F1_ATOL = 1e-6, 1e-7
+
+
+def fair_row_grad_tol(s):
+    """Bound of the per-row gradient check of the fairness penalty,
+    max_l |g[b,l] - ref[b,l]| <= tol * max_l |ref[b,l]|  for every row b (a
+    row's gradient scales with its weight, so a whole-tensor metric lets the
+    light rows be wrong).  2**-23 covers the one rounding of the fp64 value to
+    the fp32 gradient; s is the oracle's own sensitivity to summation order in
+    the same metric (the oracle on the rows in a fixed permutation, un-permuted,
+    against the oracle -- no kernel involved; measured <= 2.1e-15), taken four
+    times.  Rows whose reference is all zero must be exactly zero.  Measured
+    on the MI355X over the 58 penalty cases: <= 5.7e-8."""
+    return 2.0 ** -23 + 4.0 * s
+
+
 # Training-loop tracking (several Adam steps, ours vs the reference restated):
 # Adam's early steps move every parameter by about +-lr whatever the gradient's
 # size (m / sqrt(v) ~ sign(g)), so a parameter whose gradient sits at the
