@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MPV_ABI_VERSION 12 /* 4: device-memory Philox keys (mpv_noise_philox*_dev);
+#define MPV_ABI_VERSION 13 /* 4: device-memory Philox keys (mpv_noise_philox*_dev);
                               5: T rows padded to roundup(L, 4) floats;
                               6: mpv_linear (the VAE's Linear layers); mpv_bwd_args
                                  dR64 and kl;
@@ -51,7 +51,9 @@ extern "C" {
                                  mpv_final_args.seed_advance
                              11: mpv_curve_metrics (validation AUC / AUPR / FDR)
                              12: mpv_threshold_sweep (the threshold metrics of
-                                 up to 64 thresholds from one read of the split) */
+                                 up to 64 thresholds from one read of the split)
+                             13: mpv_calib_fwd / mpv_calib_bwd (post-process
+                                 threshold calibration) */
 
 enum mpv_status { MPV_OK = 0, MPV_EINVAL = 1, MPV_ELAUNCH = 2 };
 enum mpv_dtype { MPV_F32 = 0, MPV_F64 = 1 };
@@ -434,7 +436,8 @@ int mpv_adam_finish(const mpv_adam_finish_args* args, void* stream);
  * reparam_bwd, kl_bwd, linear, adam, adam_finish, label_weights, fair_fwd,
  * fair_bwd, metrics, curve_keys, curve_sort (the LDS chunk sort), curve_merge
  * (the merge passes), curve_pass, curve_agg, metric_sweep (every launch of
- * mpv_threshold_sweep).  Query synchronises the recorded events. */
+ * mpv_threshold_sweep), calib_fwd, calib_tables, calib_bwd.  Query
+ * synchronises the recorded events. */
 int mpv_timing_enable(int on);
 int mpv_timing_reset(void);
 int mpv_timing_query(const char* kernel, int64_t* launches, double* total_ms);
@@ -548,6 +551,47 @@ typedef struct mpv_sweep_args {
 size_t mpv_sweep_workspace_bytes(int64_t N, int64_t L, int64_t n_thr);
 int mpv_threshold_sweep(const mpv_sweep_args* args, void* workspace, size_t workspace_bytes,
                         void* stream);
+
+/* ---- Post-process threshold calibration (fairsoft_train_postprocess.py;
+ * calib.hip) -------------------------------------------------------------------
+ * One threshold per (label, sensitive group), learned on a frozen model.  With
+ * eps = 1e-6, thr = learn_logit ? 1 / (exp(-x) + 1) : x at x = threshold[l, g(b)]:
+ *   q[b, l] = 1 / (exp(-(log(p / (1 - p + eps)) - log(thr / (1 - thr + eps)))) + 1)
+ *   bce     = mean_b sum_l -(y log(q + eps) + (1 - y) log(1 - q + eps))   (:117-126)
+ *   fair    = sum over targets t with W_t > 0 and groups k with W_tk > 0 of
+ *             sum_l (m_tk[l] - m_t[l])^2,  m_tk = sum_{b in k} w q / W_tk,
+ *             m_t = sum_b w q / W_t                                        (:128-161)
+ * fp64 arithmetic from fp32 inputs; a threshold outside (0, 1) with learn_logit
+ * off gives NaN, as the reference's log does.  Rows are grouped as for
+ * mpv_fair_args: `order` (B) lists them group by group, `goff` (G + 1) holds
+ * the group offsets; a group's rows are cut into R slices, one workgroup per
+ * (256 labels, group, slice).  Every sum runs in an order fixed by (B, L, T, G,
+ * R, goff): no floating-point atomics, two calls give the same bits.  The
+ * workspace carries the backward's tables from mpv_calib_fwd to mpv_calib_bwd. */
+typedef struct mpv_calib_args {
+  const float* p;         /* (B, L) indiv_prob */
+  const float* threshold; /* (L, G) threshold_, or NULL: p is already calibrated (q = p;
+                             the evaluation's fair_mean_diff, :413-446) */
+  const float* y;         /* (B, L) labels, or NULL: no BCE (out[0] = 0) */
+  const double* w;        /* (T, B) row weights (mpv_label_weights); unused when T = 0 */
+  const int32_t* order;   /* (B) */
+  const int32_t* goff;    /* (G + 1) */
+  int64_t B, L, T, G;     /* B, L, G >= 1; T >= 0; G <= 65535 */
+  int64_t R;              /* row slices per group, 1 .. 65535 */
+  int learn_logit;        /* threshold holds logits (args.learn_logit) */
+  float* cal_prob;        /* (B, L) out: q, or NULL */
+  double* out;            /* (3) out: bce, fair, the number of (t, k) terms added */
+} mpv_calib_args;
+
+/* 0 for a bad shape. */
+size_t mpv_calib_workspace_bytes(int64_t L, int64_t T, int64_t G, int64_t R);
+int mpv_calib_fwd(const mpv_calib_args* args, void* workspace, size_t workspace_bytes,
+                  void* stream);
+/* g_threshold (L, G) and, unless NULL, g_p (B, L) = gout[0] x d bce + gout[1] x
+ * d fair (gout: two doubles in device memory), after mpv_calib_fwd on the same
+ * arguments and workspace.  Needs a threshold; an empty group's entries are 0. */
+int mpv_calib_bwd(const mpv_calib_args* args, const double* gout, float* g_threshold, float* g_p,
+                  void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

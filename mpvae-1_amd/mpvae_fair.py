@@ -48,6 +48,12 @@ Differences from the reference:
   propagates NaN: a metric that is NaN at any threshold (ebF1 or maF1 with no
   defined term, meanAUC with no two-class label) comes back NaN, where
   Python's max / min keep or drop it depending on the order.
+
+The post-process method's consumer of ``indiv_prob``
+(fairsoft_train_postprocess.py: one decision threshold per label and sensitive
+group, learned on a frozen model) runs in csrc/calib.hip: ``calibration_loss``,
+``calibrate`` and ``fair_mean_diff`` at the end of this module, with their own
+list of differences.
 """
 import ctypes
 
@@ -418,3 +424,224 @@ def best_threshold_metrics(predictions, targets, thresholds=THRESHOLDS):
     best8 = per_thr.amax(0)  # propagates NaN; none of the eight is an FDR entry
     best = {k: best8[i] for i, k in enumerate(METRIC_KEYS)}
     return {k: best[k] if k in best else curves[k] for k in METRICS}
+
+
+# ------------------------------------------------ post-process calibration
+# fairsoft_train_postprocess.py on the device (csrc/calib.hip): one decision
+# threshold per (label, sensitive group) learned on a frozen model
+# (postprocess_threshold_one_epoch, :52-198) and scored over a split
+# (evaluate_fair_through_postprocess, :304-464).  Differences from the
+# reference, none of them numeric beyond rounding:
+# * fp64 arithmetic from the fp32 probabilities and thresholds, where the
+#   reference runs calibrate_p and the BCE in fp32; ``bce`` comes back in
+#   fp32, ``fair`` in the tables' reference dtype (as ``fairness_penalty``);
+# * the fairness groups are the dataset's centroids (``centroids``), not the
+#   batch's own ``torch.unique``: the same partition, since a centroid with no
+#   row in the batch adds nothing; one group id per row serves the threshold
+#   column and the fairness groups;
+# * ``fair`` is a zero tensor and ``active`` False where the reference leaves
+#   ``fair_loss`` the Python float 0.;
+# * a row whose sensitive pattern is no centroid makes both losses NaN (the
+#   reference's boolean-mask indexing would drop the row and then fail on the
+#   shape mismatch with input_label).
+
+def centroid_ids(sensitive_feat, centroids):
+    """``(gid, unmatched)``: the index of each row's sensitive pattern among the
+    rows of ``centroids`` (``np.unique(data.sensitive_feat, axis=0)`` of the
+    whole dataset; the column ``sen_belong`` selects, :112-115) as int32 (B,),
+    and a 0-d bool that is set when some row matches no centroid (its id is
+    then 0, so that nothing indexes out of range).  Fixed-size compares, no
+    host sync; works on CPU tensors too."""
+    B, G = sensitive_feat.shape[0], centroids.shape[0]
+    if G < 1:
+        raise ValueError("centroid_ids needs at least one centroid")
+    belong = (sensitive_feat.reshape(B, 1, -1) == centroids.reshape(1, G, -1)).all(-1)  # (B, G)
+    gid = belong.to(torch.uint8).argmax(1).to(torch.int32)  # the first match; 0 when none
+    return gid, ~belong.any(1).all()
+
+
+def _group_layout(gid, G):
+    """(order, goff) of ``sensitive_groups`` for given group ids in [0, G)."""
+    order = torch.argsort(gid, stable=True).to(torch.int32)
+    counts = torch.zeros(G, dtype=torch.int32, device=gid.device)
+    counts.index_add_(0, gid.long(), torch.ones_like(gid))
+    goff = torch.zeros(G + 1, dtype=torch.int32, device=gid.device)
+    goff[1:] = torch.cumsum(counts, 0).to(torch.int32)
+    return order.contiguous(), goff
+
+
+CALIB_MIN_SLICE = 8    # rows a slice should hold before a group is cut further
+CALIB_MAX_SLICES = 64
+
+
+def calib_slices(B, L, G, device):
+    """R, the row slices per group of csrc/calib.hip's grid: enough workgroups
+    (256 labels x group x slice) for two per compute unit, while a slice of an
+    evenly filled group keeps CALIB_MIN_SLICE rows.  Host knowledge only."""
+    cus = torch.cuda.get_device_properties(device).multi_processor_count
+    blocks = ((L + 255) // 256) * G
+    want = (2 * cus + blocks - 1) // blocks
+    return max(1, min(want, B // (G * CALIB_MIN_SLICE), CALIB_MAX_SLICES))
+
+
+def _calib_fwd(p, x, y, w, order, goff, G, R, learn_logit, want_cal):
+    """mpv_calib_fwd on contiguous device tensors -> (out (3,) fp64, cal_prob,
+    and what the backward needs)."""
+    B, L = p.shape
+    T = 0 if w is None else w.shape[0]
+    lib = H.load_library()
+    nbytes = lib.mpv_calib_workspace_bytes(L, T, G, R)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=p.device)
+    out = torch.empty(3, dtype=torch.float64, device=p.device)
+    cal = torch.empty_like(p) if want_cal else None
+    a = H.CalibArgs(H.ptr(p), H.ptr(x), H.ptr(y), H.ptr(w), H.ptr(order), H.ptr(goff), B, L, T, G,
+                    R, int(bool(learn_logit)), H.ptr(cal), H.ptr(out))
+    H.check(lib.mpv_calib_fwd(ctypes.byref(a), H.ptr(ws), nbytes, H.stream_of(p.device)),
+            "mpv_calib_fwd")
+    return out, cal, (a, ws, nbytes)
+
+
+class _Calibration(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, indiv_prob, threshold_, y, w, order, goff, G, R, learn_logit):
+        p = indiv_prob.detach().contiguous().float()
+        x = threshold_.detach().contiguous().float()
+        out, cal, state = _calib_fwd(p, x, y, w, order, goff, G, R, learn_logit, True)
+        ctx.keep = (p, x, y, w, order, goff) + state
+        ctx.meta = (indiv_prob.dtype, threshold_.dtype, threshold_.shape)
+        nterms = out[2]
+        ctx.mark_non_differentiable(cal, nterms)
+        return out[0], out[1], cal, nterms
+
+    @staticmethod
+    def backward(ctx, g_bce, g_fair, _g_cal, _g_n):
+        p, x, y, w, order, goff, a, ws, nbytes = ctx.keep
+        zero = torch.zeros((), dtype=torch.float64, device=p.device)
+        gout = torch.stack([zero if g is None else g.detach().to(torch.float64)
+                            for g in (g_bce, g_fair)])
+        gx = torch.empty_like(x)
+        gp = torch.empty_like(p) if ctx.needs_input_grad[0] else None
+        lib = H.load_library()
+        H.check(lib.mpv_calib_bwd(ctypes.byref(a), H.ptr(gout), H.ptr(gx), H.ptr(gp), H.ptr(ws),
+                                  nbytes, H.stream_of(p.device)), "mpv_calib_bwd")
+        pdt, xdt, xshape = ctx.meta
+        return (None if gp is None else gp.to(pdt), gx.to(xdt).reshape(xshape)) + (None,) * 7
+
+
+class _ZeroCalibration(torch.autograd.Function):
+    """An empty batch: zero losses that are still differentiable functions of
+    both inputs, with zero gradients, and no launch (``_ZeroPenalty``'s
+    precedent)."""
+
+    @staticmethod
+    def forward(ctx, indiv_prob, threshold_):
+        ctx.save_for_backward(indiv_prob, threshold_)
+        z = torch.zeros((), dtype=torch.float64, device=indiv_prob.device)
+        return z, z.clone()
+
+    @staticmethod
+    def backward(ctx, g_bce, g_fair):
+        return tuple(torch.zeros_like(t) for t in ctx.saved_tensors)
+
+
+def _check_threshold(threshold_, L, G):
+    if threshold_.numel() != L * G or tuple(threshold_.shape[-2:]) != (L, G):
+        raise ValueError(f"threshold of shape {tuple(threshold_.shape)} is not (1, {L}, {G}) "
+                         "(label_dim, number of centroids)")
+
+
+def calibration_loss(indiv_prob, threshold_, input_label, sensitive_feat, centroids, tables,
+                     learn_logit, slices=None):
+    """fairsoft_train_postprocess.py:112-165 on the device.
+
+    indiv_prob     -- (B, L) compute_loss output 7
+    threshold_     -- (1, L, G) the learned thresholds (logits when ``learn_logit``)
+    input_label    -- (B, L) batch labels
+    sensitive_feat -- (B, n_sensitive) of the batch
+    centroids      -- (G, n_sensitive) ``np.unique(data.sensitive_feat, axis=0)``
+    tables         -- [LabelDistanceTable(label_distances[t], L, dev) for t in
+                      target_fair_labels]; ``[]``: the BCE alone
+    slices         -- row slices per group of the kernels' grid (default:
+                      ``calib_slices``); the results agree to fp64 rounding
+    Returns ``(bce, fair, cal_prob, active, contributed)``: ``bce`` (fp32) and
+    ``fair`` (the tables' reference dtype; not yet times ``fair_coeff``) are
+    differentiable 0-d tensors of ``threshold_`` and, where it requires a
+    gradient, ``indiv_prob``; ``cal_prob`` (B, L) fp32 carries no gradient (the
+    reference reads it for metrics only); ``active`` is a 0-d bool, set when at
+    least one (target, group) term was added (the reference's ``not
+    isinstance(fair_loss, float)``, :163: only then is the total ``fair *
+    fair_coeff + bce``); ``contributed`` is the int32 count the reference adds
+    to contributed_reg_fair_sample.  A row that matches no centroid makes both
+    losses NaN.  No host sync: forward and backward can be captured in a HIP
+    graph."""
+    H.require_gpu(indiv_prob, threshold_, input_label, sensitive_feat, centroids)
+    B, L = indiv_prob.shape
+    G = centroids.shape[0]
+    _check_threshold(threshold_, L, G)
+    dev = indiv_prob.device
+    fdt = torch.float32 if tables and all(t.ref_dtype == torch.float32 for t in tables) \
+        else torch.float64
+    if B == 0:  # shapes are host knowledge: no sync, still capturable
+        bce, fair = _ZeroCalibration.apply(indiv_prob, threshold_)
+        return (bce.float(), fair.to(fdt), torch.empty_like(indiv_prob, dtype=torch.float32),
+                torch.zeros((), dtype=torch.bool, device=dev),
+                torch.zeros((), dtype=torch.int32, device=dev))
+    y = input_label.detach().contiguous().float()
+    if tables:
+        w, count = label_weights(y, tables)
+    else:
+        w, count = None, torch.zeros((), dtype=torch.int32, device=dev)
+    gid, unmatched = centroid_ids(sensitive_feat, centroids)
+    order, goff = _group_layout(gid, G)
+    R = calib_slices(B, L, G, dev) if slices is None else int(slices)
+    bce, fair, cal_prob, nterms = _Calibration.apply(indiv_prob, threshold_, y, w, order, goff, G,
+                                                     R, learn_logit)
+    nan = torch.full_like(bce, float("nan"))
+    bce = torch.where(unmatched, nan, bce).float()
+    fair = torch.where(unmatched, nan, fair).to(fdt)
+    return bce, fair, cal_prob, nterms > 0, count
+
+
+def calibrate(indiv_prob, threshold, sensitive_feat, centroids, slices=None):
+    """``calibrate_p(indiv_prob.unsqueeze(-1), threshold).transpose(1, 2)[sen_belong]``
+    (:379-381): (B, L) fp32 calibrated probabilities, each row with the
+    thresholds of its own group.  ``threshold`` (1, L, G) holds probabilities:
+    no sigmoid is applied (the evaluation's caller has applied it when the
+    thresholds were learned as logits).  A row that matches no centroid comes
+    back NaN.  Forward only, no host sync."""
+    H.require_gpu(indiv_prob, threshold, sensitive_feat, centroids)
+    p = indiv_prob.detach().contiguous().float()
+    B, L = p.shape
+    G = centroids.shape[0]
+    _check_threshold(threshold, L, G)
+    if B == 0:
+        return torch.empty_like(p)
+    gid, unmatched = centroid_ids(sensitive_feat, centroids)
+    order, goff = _group_layout(gid, G)
+    R = calib_slices(B, L, G, p.device) if slices is None else int(slices)
+    x = threshold.detach().contiguous().float()
+    _, cal, _ = _calib_fwd(p, x, None, None, order, goff, G, R, False, True)
+    rows = (sensitive_feat.reshape(B, 1, -1) == centroids.reshape(1, G, -1)).all(-1).any(1)
+    return torch.where(rows[:, None], cal, torch.full_like(cal, float("nan")))
+
+
+def fair_mean_diff(cal_prob, labels, sensitive_feat, centroids, tables, slices=None):
+    """``best_val_metrics['fair_mean_diff']`` of evaluate_fair_through_postprocess
+    (:413-446) over a whole split: the mean over the active (target, group)
+    terms of the squared distance between the group's and the split's weighted
+    mean of ``cal_prob``; a 0-d fp64 device tensor, NaN when no term is active
+    (the reference's ``np.mean([])``) or a row matches no centroid.  No host
+    sync."""
+    H.require_gpu(cal_prob, labels, sensitive_feat, centroids)
+    q = cal_prob.detach().contiguous().float()
+    B, L = q.shape
+    nan = torch.full((), float("nan"), dtype=torch.float64, device=q.device)
+    if B == 0 or not tables:
+        return nan
+    w, _ = label_weights(labels, tables)
+    G = centroids.shape[0]
+    gid, unmatched = centroid_ids(sensitive_feat, centroids)
+    order, goff = _group_layout(gid, G)
+    R = calib_slices(B, L, G, q.device) if slices is None else int(slices)
+    out, _, _ = _calib_fwd(q, None, None, w, order, goff, G, R, False, False)
+    return torch.where(unmatched | (out[2] == 0), nan, out[1] / out[2])

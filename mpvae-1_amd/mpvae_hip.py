@@ -13,7 +13,7 @@ import torch  # noqa: F401  (must precede the .so load: one HIP runtime per proc
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MPVAE_HIP_LIB", os.path.join(HERE, "libmpvae_hip.so"))
 
-ABI_VERSION = 12
+ABI_VERSION = 13
 F32, F64 = 0, 1
 G_TOTAL, G_NLL, G_NLL_X, G_C, G_C_X, G_KL = range(6)
 
@@ -153,6 +153,14 @@ class SweepArgs(ctypes.Structure):
                 ("n_thr", ctypes.c_int64), ("thr", ctypes.c_float * MAX_THRESHOLDS), ("out", vp)]
 
 
+class CalibArgs(ctypes.Structure):
+    """mpv_calib_args: post-process threshold calibration (calib.hip)."""
+    _fields_ = [("p", vp), ("threshold", vp), ("y", vp), ("w", vp), ("order", vp), ("goff", vp),
+                ("B", ctypes.c_int64), ("L", ctypes.c_int64), ("T", ctypes.c_int64),
+                ("G", ctypes.c_int64), ("R", ctypes.c_int64), ("learn_logit", ctypes.c_int),
+                ("cal_prob", vp), ("out", vp)]
+
+
 # name -> (restype, argtypes); exactly the symbols of include/mpvae_hip.h
 SIGNATURES = {
     "mpv_abi_version": (ctypes.c_int, []),
@@ -213,6 +221,11 @@ SIGNATURES = {
     "mpv_sweep_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64,
                                                     ctypes.c_int64]),
     "mpv_threshold_sweep": (ctypes.c_int, [ctypes.POINTER(SweepArgs), vp, ctypes.c_size_t, vp]),
+    "mpv_calib_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64,
+                                                    ctypes.c_int64, ctypes.c_int64]),
+    "mpv_calib_fwd": (ctypes.c_int, [ctypes.POINTER(CalibArgs), vp, ctypes.c_size_t, vp]),
+    "mpv_calib_bwd": (ctypes.c_int, [ctypes.POINTER(CalibArgs), vp, vp, vp, vp, ctypes.c_size_t,
+                                     vp]),
 }
 
 _lib = None
@@ -276,7 +289,7 @@ KERNELS = ["noise_philox", "split", "probit_fwd", "fwd_combine", "finalize", "bw
            "dR_gemm", "sum_slabs", "convert", "bstat_combine", "reparam_fwd", "reparam_bwd",
            "kl_bwd", "label_weights", "fair_fwd", "fair_bwd", "metrics", "linear", "adam",
            "adam_finish", "curve_keys", "curve_sort", "curve_merge", "curve_pass", "curve_agg",
-           "metric_sweep"]
+           "metric_sweep", "calib_fwd", "calib_tables", "calib_bwd"]
 
 
 def kernel_times():

@@ -399,3 +399,95 @@ class TrainStep:
         with torch.cuda.graph(self.graph):
             self.out = self._body(self.label, self.feat)
         return self.graph
+
+
+class CalibrationStep(TrainStep):
+    """The loop body of postprocess_threshold_one_epoch
+    (fairsoft_train_postprocess.py:84-175) as one call: the frozen model's
+    ``model(label, feat)`` -> ``compute_loss`` (for ``indiv_prob``) ->
+    ``mpvae_fair.calibration_loss`` -> ``backward`` -> finite-gradient gate ->
+    Adam step on ``threshold_`` -> StepLR, all on the device.
+
+    ``step(label, feat, sensitive_feat)`` returns ``(total, bce, fair,
+    cal_prob, contributed)`` as device tensors.  ``total`` is ``fair *
+    args.fair_coeff + bce`` when at least one fairness term was added and
+    compute_loss's own total otherwise (:163-165); in such a batch the
+    threshold's gradient is multiplied by 0 on the device and the update still
+    applies (weight decay and the Adam moments move the threshold), as the
+    reference's ``optimizer.step()`` on its zeroed gradients did.  ``updates``
+    counts the applied steps (succses_updates).  ``args`` is compute_loss's
+    namespace plus ``fair_coeff`` and ``learn_logit``; ``args.mode`` is used as
+    given ('train': ``n_train_sample`` noise draws, as the reference runs it).
+    ``tables`` and ``centroids`` are those of ``calibration_loss``.  The model
+    is put in ``eval()`` mode, as the reference does.
+
+    Differences from the reference:
+    * no autograd through ``compute_loss`` and the model (they run under
+      ``torch.no_grad()``): the threshold's gradient does not depend on it, and
+      the reference's own backward through them fed nothing that was read;
+    * the reference accumulates model gradients that it never clears or reads;
+      the step produces none;
+    * r_sqrt_sigma is the model's (the reference's ``residue_sigma ==
+      "random"`` host draw is not reproduced, as in TrainStep).
+
+    The optimizer must be a plain fused ``torch.optim.Adam([threshold_], ...,
+    fused=True)`` (it steps in ``adam_step``), with ``capturable=True`` for
+    ``capture()``; ``scheduler`` is the reference's StepLR or None.  With Philox
+    noise and a device seed nothing waits for the host."""
+
+    def __init__(self, model, threshold_, optimizer, args, tables, centroids, scheduler=None):
+        if not _native_adam(optimizer):
+            raise ValueError("CalibrationStep steps a plain fused Adam on the device: use "
+                             "torch.optim.Adam([threshold_], ..., fused=True) with a float lr")
+        if not (threshold_.is_leaf and threshold_.requires_grad):
+            raise ValueError("threshold_ must be a leaf tensor that requires a gradient")
+        self.model, self.opt, self.args = model.eval(), optimizer, args
+        self.threshold_, self.tables, self.centroids = threshold_, tables, centroids
+        self.advance_seed, self.native_adam = True, True
+        self.params = [threshold_]
+        dev = threshold_.device
+        self.updates = torch.zeros((), dtype=torch.int64, device=dev)
+        self.found_inf = torch.zeros((), dtype=torch.float32, device=dev)
+        self._one = torch.ones((), dtype=torch.float32, device=dev)
+        self.sched = None if scheduler is None else DeviceStepLR(scheduler, optimizer)
+        self.graph = None
+        self.label = self.feat = self.sens = self.out = None
+
+    def _body(self, label, feat):
+        import mpvae
+        import mpvae_fair
+        self.opt.zero_grad(set_to_none=True)
+        args = self.args
+        if isinstance(getattr(args, "mpvae_seed", None), torch.Tensor):
+            args = copy.copy(self.args)  # fresh probit noise every step (TrainStep._body)
+            args.mpvae_seed_advance = True
+        with torch.no_grad():
+            out = self.model(label, feat)
+            res = mpvae.compute_loss(label, *out, self.model.r_sqrt_sigma, args)
+        bce, fair, cal_prob, active, contributed = mpvae_fair.calibration_loss(
+            res[6], self.threshold_, label, self.sens, self.centroids, self.tables,
+            args.learn_logit)
+        cal_total = fair * args.fair_coeff + bce
+        total = torch.where(active, cal_total.detach(), res[0].to(cal_total.dtype))
+        (cal_total * active.to(cal_total.dtype)).backward()
+        self.found_inf.zero_()
+        torch._amp_foreach_non_finite_check_and_unscale_([self.threshold_.grad], self.found_inf,
+                                                         self._one)
+        adam_step(self.opt, self.found_inf, self.updates, self.sched)
+        return total, bce.detach(), fair.detach(), cal_prob, contributed
+
+    def __call__(self, label, feat, sensitive_feat):
+        """One step (a replay once captured) on the batch."""
+        if self.graph is not None:
+            self.sens.copy_(sensitive_feat)
+        else:
+            self.sens = sensitive_feat
+        return super().__call__(label, feat)
+
+    step = __call__
+
+    def capture(self, label, feat, sensitive_feat, warmup=2):
+        """TrainStep.capture with the batch's sensitive features as a third
+        static buffer."""
+        self.sens = sensitive_feat.clone()
+        return super().capture(label, feat, warmup)
