@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MPV_ABI_VERSION 13 /* 4: device-memory Philox keys (mpv_noise_philox*_dev);
+#define MPV_ABI_VERSION 14 /* 4: device-memory Philox keys (mpv_noise_philox*_dev);
                               5: T rows padded to roundup(L, 4) floats;
                               6: mpv_linear (the VAE's Linear layers); mpv_bwd_args
                                  dR64 and kl;
@@ -53,7 +53,9 @@ extern "C" {
                              12: mpv_threshold_sweep (the threshold metrics of
                                  up to 64 thresholds from one read of the split)
                              13: mpv_calib_fwd / mpv_calib_bwd (post-process
-                                 threshold calibration) */
+                                 threshold calibration)
+                             14: mpv_probit_predict (label-free prediction:
+                                 indiv_prob alone from a lean forward) */
 
 enum mpv_status { MPV_OK = 0, MPV_EINVAL = 1, MPV_ELAUNCH = 2 };
 enum mpv_dtype { MPV_F32 = 0, MPV_F64 = 1 };
@@ -182,6 +184,34 @@ size_t mpv_fwd_workspace_bytes(const mpv_shape* shape);
  * as P*N), the shard-local log-sum-exp statistics (:188-189) and the sums
  * over s behind indiv_prob / indiv_prob_label (:203-204). */
 int mpv_probit_fwd(const mpv_shape* shape, const mpv_fwd_args* args, void* stream);
+
+/* ------------------------------------------------------------- prediction */
+typedef struct mpv_predict_args {
+  const float* fx_out;  /* (B, L) */
+  int gemm;             /* mpv_gemm; the operands below as in mpv_fwd_args */
+  const float* R32;
+  const float* eps;
+  mpv_split16 R16;
+  mpv_split16 eps16;
+  float* colsum;          /* (B, L) out: this shard's sum over s of E_x */
+  float* indiv_prob;      /* (B, L) out = colsum / S_total, or NULL (a sharded caller divides
+                             after its all-reduce) */
+  uint64_t* seed_advance; /* as mpv_final_args, or NULL */
+  void* workspace;
+  size_t workspace_bytes;
+} mpv_predict_args;
+
+/* The column partials only; 0 for a bad shape (and for a shape whose tiles
+ * write colsum directly). */
+size_t mpv_predict_workspace_bytes(const mpv_shape* shape);
+
+/* indiv_prob = mean_s E_x (mpvae.py:180, :203) from fx_out, r_sqrt_sigma and
+ * the noise alone: no labels, no label branch, no loss terms.  The tile, the
+ * s-chunks, the GEMM and every operation on the feature branch's values are
+ * mpv_probit_fwd's, and the sums run in its order, so colsum and indiv_prob
+ * equal mpv_probit_fwd + mpv_probit_finalize's colsum[1] and indiv_prob bit
+ * for bit.  Arguments are checked as mpv_probit_fwd's, before any launch. */
+int mpv_probit_predict(const mpv_shape* shape, const mpv_predict_args* args, void* stream);
 
 /* Exact combine of per-shard bstat gathered as (nshards,6,B) -> (6,B):
  * M = max m_r, Z = sum Z_r exp(m_r - M), ranking sums add. */
@@ -436,8 +466,9 @@ int mpv_adam_finish(const mpv_adam_finish_args* args, void* stream);
  * reparam_bwd, kl_bwd, linear, adam, adam_finish, label_weights, fair_fwd,
  * fair_bwd, metrics, curve_keys, curve_sort (the LDS chunk sort), curve_merge
  * (the merge passes), curve_pass, curve_agg, metric_sweep (every launch of
- * mpv_threshold_sweep), calib_fwd, calib_tables, calib_bwd.  Query
- * synchronises the recorded events. */
+ * mpv_threshold_sweep), calib_fwd, calib_tables, calib_bwd, probit_predict,
+ * predict_final (the two launches of mpv_probit_predict).  Query synchronises
+ * the recorded events. */
 int mpv_timing_enable(int on);
 int mpv_timing_reset(void);
 int mpv_timing_query(const char* kernel, int64_t* launches, double* total_ms);

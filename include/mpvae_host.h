@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define MPVH_ABI_VERSION 1
+#define MPVH_ABI_VERSION 2 /* 2: mpvh_probit_predict */
 
 int mpvh_abi_version(void);
 const char* mpvh_last_error(void);
@@ -54,6 +54,14 @@ typedef struct mpvh_fwd_args {
 } mpvh_fwd_args;
 
 int mpvh_probit_fwd(const mpv_shape* shape, const mpvh_fwd_args* args);
+
+/* Label-free prediction (mpv_probit_predict's host twin): colsum (B,L) = this
+ * shard's sum over s of E_x, the feature-branch half of mpvh_probit_fwd -- the
+ * same t, the same E, the same sum order, so colsum equals mpvh_probit_fwd's
+ * colsum[1] bit for bit, and colsum / S_total rounded to fp32 its
+ * indiv_prob.  R is (L,z) fp32 or fp64 (R_dtype), eps (S_local,B,z). */
+int mpvh_probit_predict(const mpv_shape* shape, const float* fx_out, const void* R, int R_dtype,
+                        const float* eps, double* colsum);
 
 /* Exact combine of per-shard bstat gathered as (nshards,6,B) -> (6,B). */
 int mpvh_bstat_combine(const double* gathered, int64_t nshards, int64_t B, double* out);

@@ -30,6 +30,14 @@
 //                        partials, writes rowstat, the shard's log-sum-exp
 //                        statistics (m, Z) and ranking sums.
 //   finalize_kernel      the 8 outputs of compute_loss (+ KL, mpvae.py:147-148).
+//   The label-free prediction (mpv_probit_predict: indiv_prob alone) runs the
+//   PREDICT instantiations of the same tile kernels -- the K loop unchanged,
+//   the epilogue reduced to the feature branch's probit and its column sums
+//   (fwd_tile_epilogue_predict_t / fwd_tile_epilogue_predict), bit for bit the
+//   sums of the full forward -- and
+//   predict_final_kernel the s-chunk partials summed in the full forward's
+//                        order, indiv_prob = colsum / S_total, the device
+//                        Philox key's advance.
 //
 // Tiling: a workgroup owns one batch row b, one label tile [n0, n0+BN) and a
 // chunk of s-tiles of BM samples; the GEMM's M axis is s (eps rows for fixed
@@ -175,6 +183,15 @@ MPV_DEV void fwd_cols_stage_t(float* cols, const FwdParams& p, int b, int n0, in
   }
 }
 
+// The prediction variant's layout (BN floats): fx_out * kZq alone.
+template <int BN>
+MPV_DEV void fwd_cols_stage_predict(float* cols, const FwdParams& p, int b, int n0, int nthreads) {
+  for (int i = threadIdx.x; i < BN; i += nthreads) {
+    const int col = n0 + i;
+    cols[i] = col < p.L ? p.fx[(int64_t)b * p.L + col] * kZq : 0.0f;
+  }
+}
+
 // One BM x BN tile of t (acc * scale) starting at sample row s0: probit
 // decode, row statistics written to rowpart[., nt, b, s], column sums
 // accumulated in `ln`, for the rows s_own <= s < S this tile owns.  Called by
@@ -252,14 +269,70 @@ MPV_DEV void fwd_tile_epilogue(const FwdParams& p, FwdLane<TN>& ln, f32x4 (&acc)
   lds_barrier();
 }
 
-// Column sums of this workgroup -> colpart[sc, ., b, n0 ...].
+// fwd_tile_epilogue of the prediction path (mpv_probit_predict): the feature
+// branch's E alone, summed over the tile's own rows into ln.col[n].y with the
+// operations and in the order of fwd_tile_epilogue (probit_eval2 is
+// element-wise, so .y carries the full epilogue's bits); no labels, no row
+// statistics, no T, no LDS.
 template <int WM, int WN, int TM, int TN>
+MPV_DEV void fwd_tile_epilogue_predict(const FwdParams& p, FwdLane<TN>& ln, f32x4 (&acc)[TM][TN],
+                                       float scale, int b, int s0, int s_own, int nt) {
+  constexpr int BN = WN * TN * 16;
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int wm = wid / WN, wn = wid % WN, lr = lane & 15, lg = lane >> 4;
+  float fx[TN];
+#pragma unroll
+  for (int n = 0; n < TN; ++n) {
+    const int col = nt * BN + wn * TN * 16 + n * 16 + lr;
+    fx[n] = p.fx[(int64_t)b * p.L + (col < p.L ? col : 0)];
+  }
+#pragma unroll
+  for (int m = 0; m < TM; ++m) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int s = s0 + wm * TM * 16 + m * 16 + lg * 4 + i;
+      const bool rowok = s >= s_own && s < p.S;
+#pragma unroll
+      for (int n = 0; n < TN; ++n) {
+        const float t = acc[m][n][i] * scale;
+        f32x2 phi;
+        const f32x2 E = probit_eval2(splat2(t) + splat2(fx[n]), phi);
+        ln.col[n] += rowok ? E : splat2(0.0f);
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);  // bound live ranges to one m-slab
+  }
+}
+
+// Column sums of this workgroup -> colpart[sc, ., b, n0 ...]; PREDICT: the
+// feature branch's alone -> colpart[sc, b, n0 ...].
+template <int WM, int WN, int TM, int TN, bool PREDICT = false>
 MPV_DEV void fwd_colsum_epilogue(const FwdParams& p, FwdLane<TN>& ln, int b, int sc, int n0,
                                  float* smem) {
   constexpr int NT = WM * WN * 64, BN = WN * TN * 16;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wm = wid / WN, wn = wid % WN, lr = lane & 15, lg = lane >> 4;
   float* cred = smem;  // [WM][BN][2]
+  if constexpr (PREDICT) {
+#pragma unroll
+    for (int n = 0; n < TN; ++n) {
+      float x = ln.col[n].y;
+      x += __shfl_xor(x, 16, 64);
+      x += __shfl_xor(x, 32, 64);
+      if (lg == 0) cred[wm * BN + wn * TN * 16 + n * 16 + lr] = x;
+    }
+    __syncthreads();
+    for (int c = tid; c < BN; c += NT) {
+      const int col = n0 + c;
+      if (col < p.L) {
+        float x = 0.f;
+#pragma unroll
+        for (int w = 0; w < WM; ++w) x += cred[w * BN + c];
+        p.colpart[((int64_t)sc * p.B + b) * p.L + col] = x;
+      }
+    }
+    return;
+  }
 #pragma unroll
   for (int n = 0; n < TN; ++n) {
     float e = ln.col[n].x, x = ln.col[n].y;
@@ -301,7 +374,7 @@ MPV_DEV void fwd_colsum_epilogue(const FwdParams& p, FwdLane<TN>& ln, int b, int
 #else
 #define MPV_NO_PK_FP32
 #endif
-template <int WM, int WN, int TM, int TN>
+template <int WM, int WN, int TM, int TN, bool PREDICT = false>
 __global__ MPV_NO_PK_FP32 __launch_bounds__(WM* WN * 64) void probit_fwd_kernel(FwdParams p) {
   constexpr int NT = WM * WN * 64;
   constexpr int BM = WM * TM * 16;
@@ -425,9 +498,12 @@ __global__ MPV_NO_PK_FP32 __launch_bounds__(WM* WN * 64) void probit_fwd_kernel(
         __syncthreads();
       }
     }
-    fwd_tile_epilogue<WM, WN, TM, TN>(p, ln, acc, 1.0f, b, s0, s0, nt, smem);
+    if constexpr (PREDICT)
+      fwd_tile_epilogue_predict<WM, WN, TM, TN>(p, ln, acc, 1.0f, b, s0, s0, nt);
+    else
+      fwd_tile_epilogue<WM, WN, TM, TN>(p, ln, acc, 1.0f, b, s0, s0, nt, smem);
   }
-  fwd_colsum_epilogue<WM, WN, TM, TN>(p, ln, b, sc, n0, smem);
+  fwd_colsum_epilogue<WM, WN, TM, TN, PREDICT>(p, ln, b, sc, n0, smem);
 }
 
 // ------------------------------------------------------ 3xf16 mainloop
@@ -775,9 +851,12 @@ struct Fwd16Ctx {
 };
 
 // Decodes the block, stages the label constants into `cols` and zeroes `cacc`.
-template <class Tile>
+// PREDICT (mpv_probit_predict): cols holds fx_out * kZq alone, cacc one float
+// per slot, and no label is read.
+template <class Tile, bool PREDICT = false>
 MPV_DEV Fwd16Ctx fwd16_ctx(const FwdParams& p, float* cacc, float* cols) {
-  constexpr int WL = Tile::WL, BN = Tile::BN, CACC = Tile::WS * Tile::CQ * BN * 2;
+  constexpr int WL = Tile::WL, BN = Tile::BN,
+                CACC = Tile::WS * Tile::CQ * BN * (PREDICT ? 1 : 2);
   Fwd16Ctx c;
   int g;
   decode_block(blockIdx.x, p.B * p.nSc, p.nNt, g, c.nt);
@@ -792,9 +871,15 @@ MPV_DEV Fwd16Ctx fwd16_ctx(const FwdParams& p, float* cacc, float* cols) {
   const int sw = (c.lr >> 1) & 7;
   c.coh = (c.lg ^ sw) << 4, c.col = ((4 + c.lg) ^ sw) << 4;
   c.t_begin = c.sc * p.tps, c.t_end = min(p.nSt, (c.sc + 1) * p.tps);
-  fwd_cols_stage_t<BN>(cols, p, c.b, c.n0, kFwd16Threads);
+  if constexpr (PREDICT)
+    fwd_cols_stage_predict<BN>(cols, p, c.b, c.n0, kFwd16Threads);
+  else
+    fwd_cols_stage_t<BN>(cols, p, c.b, c.n0, kFwd16Threads);
   for (int i = tid; i < CACC; i += kFwd16Threads) cacc[i] = 0.0f;
-  c.soft_any = fwd_tile_soft<BN>(p, c.b, c.n0, kFwd16Threads);
+  if constexpr (PREDICT)
+    c.soft_any = false;  // (the K loop's first barrier orders these LDS writes)
+  else
+    c.soft_any = fwd_tile_soft<BN>(p, c.b, c.n0, kFwd16Threads);
   c.cacc = cacc, c.cols = cols;
   return c;
 }
@@ -1060,11 +1145,112 @@ MPV_DEV void fwd_tile_epilogue_t(const FwdParams& p, const Fwd16Ctx c, f32x4 (&a
   lds_barrier();
 }
 
+// fwd_tile_epilogue_t of the prediction path (mpv_probit_predict): the feature
+// branch's column sums of E alone.  Per element the operations of the full
+// epilogue's .y half, each element-wise (fma(t, kZq, fx kZq), probit_w2xN_zq,
+// E = w kEh + C0 rounded twice, ce = fma(wr, E, ce) over the same sample
+// blocks in the same order, the same DPP column reduction into the same
+// (ws, slot, label) cacc slots), so the sums carry compute_loss's bits; packed
+// over the label pairs (0,1) and (2,3) of the lane's four labels, where the
+// full epilogue packs the two branches of one label.  No labels, no T, no
+// row statistics, no `red` exchange and none of its barriers.  The priority
+// alternation of the label loop is kept (the two waves of a SIMD still share
+// its VALU), and so are the parts of Tile::EPI_PART sample blocks
+// (fwd16_epilogue): each part's sums enter cacc separately in the full
+// path, so the parts are part of the summation order.
+template <class Tile, int TS>
+MPV_DEV void fwd_tile_epilogue_predict_t(const FwdParams& p, const Fwd16Ctx c,
+                                         f32x4 (&acc)[Tile::TL][TS], int s0, int s_own, int sbo) {
+  constexpr int WL = Tile::WL, TL = Tile::TL, BN = Tile::BN, NT = kFwd16Threads;
+  const int tid = threadIdx.x, lr = c.lr, lg = c.lg;
+  const int wid = tid >> 6, wl = wid % WL, ws = wid / WL;  // per lane, as fwd_tile_epilogue_t
+  if constexpr (Tile::TSA == Tile::TSB) {
+    static_assert(TS == Tile::TSA, "the even-split tiles run the epilogue whole");
+    sbo = ws * TS;
+  }
+  const int S = p.S;
+  const float scale = c.scale;
+  float* cacc = c.cacc;
+  const float* cols = c.cols;
+#pragma unroll
+  for (int m = 0; m < TL; ++m)
+#pragma unroll
+    for (int n = 0; n < TS; ++n) acc[m][n] = acc[m][n] * scale;  // t (exact: power of 2)
+#pragma unroll 1
+  for (int m = 0; m < TL; ++m) {
+    f32x4 am[TS];
+#pragma unroll
+    for (int n = 0; n < TS; ++n) am[n] = acc[0][n];
+#pragma unroll
+    for (int mm = 0; mm + 1 < TL; ++mm)
+#pragma unroll
+      for (int n = 0; n < TS; ++n) acc[mm][n] = acc[mm + 1][n];
+    const int lb = (wl * TL + m) * 16 + lg * 4;  // first of the lane's 4 labels in the tile
+    if (((m + __builtin_amdgcn_readfirstlane(wid / (NT / 128))) & 1) != 0)
+      __builtin_amdgcn_s_setprio(1);
+    else
+      __builtin_amdgcn_s_setprio(0);
+    const f32x4 fx4 = *reinterpret_cast<const f32x4*>(cols + lb);  // fx kZq of the 4 labels
+    const f32x2 fx2[2] = {f32x2{fx4[0], fx4[1]}, f32x2{fx4[2], fx4[3]}};
+    f32x2 ce[2] = {splat2(0.0f), splat2(0.0f)};
+#pragma unroll
+    for (int n = 0; n < TS; ++n) {
+      const int s = s0 + (sbo + n) * 16 + lr;
+      const float wr = (s >= s_own && s < S) ? 1.0f : 0.0f;
+      const f32x4 t4 = am[n];
+      f32x2 zq[2], w2[2];
+      zq[0] = pk_fma(f32x2{t4[0], t4[1]}, splat2(kZq), fx2[0]);
+      zq[1] = pk_fma(f32x2{t4[2], t4[3]}, splat2(kZq), fx2[1]);
+      probit_w2xN_zq<2>(zq, w2);
+      f32x2 E2[2];
+      {
+#pragma clang fp contract(off)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) E2[j] = w2[j] * kEh + splat2(kC0);
+      }
+#pragma unroll
+      for (int j = 0; j < 2; ++j) ce[j] = pk_fma(splat2(wr), E2[j], ce[j]);
+      if ((n + 1) % Tile::EPI_BLOCKS == 0) __builtin_amdgcn_sched_barrier(0);
+    }
+    float cs[4] = {ce[0].x, ce[0].y, ce[1].x, ce[1].y};
+    if (Tile::CQ == 4) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) cs[j] = dpp_f<0x111>(cs[j]) + cs[j];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) cs[j] = dpp_f<0x112>(cs[j]) + cs[j];
+      if ((lr & 3) == 3) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) cacc[(ws * 4 + (lr >> 2)) * BN + lb + i] += cs[i];
+      }
+    } else {
+      row16_sum_to_lane15_n<4>(cs);
+      if (lr == 15) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) cacc[ws * BN + lb + i] += cs[i];
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);  // bound live ranges to one label group
+  }
+}
+
 // Column partials of a transposed-tile workgroup -> colpart[sc, ., b, n0 ...]
-// (summing cacc's NSLOT slots per label)
-template <int NSLOT, int BN>
+// (summing cacc's NSLOT slots per label); PREDICT: one float per slot ->
+// colpart[sc, b, n0 ...]
+template <int NSLOT, int BN, bool PREDICT = false>
 MPV_DEV void fwd16t_colpart(const FwdParams& p, const float* cacc, int b, int sc, int n0) {
   lds_barrier();
+  if constexpr (PREDICT) {
+    for (int c = threadIdx.x; c < BN; c += kFwd16Threads) {
+      const int l = n0 + c;
+      if (l < p.L) {
+        float x = 0.f;
+#pragma unroll
+        for (int w = 0; w < NSLOT; ++w) x += cacc[w * BN + c];
+        p.colpart[((int64_t)sc * p.B + b) * p.L + l] = x;
+      }
+    }
+    return;
+  }
   for (int c = threadIdx.x; c < BN; c += kFwd16Threads) {
     const int l = n0 + c;
     if (l < p.L) {
@@ -1122,11 +1308,26 @@ MPV_DEV void fwd16_stage_ahead(f32x4 (&acc)[Tile::TL][TSW], const char* base, in
 
 // A tile's epilogue: whole, or in parts of Tile::EPI_PART sample blocks (the
 // row statistics of one part in registers at a time).
-template <class Tile, int TSW, int PART = 0>
+template <class Tile, int TSW, int PART = 0, bool PREDICT = false>
 MPV_DEV void fwd16_epilogue(const FwdParams& p, const Fwd16Ctx c, f32x4 (&acc)[Tile::TL][TSW], int s0,
                             int s_own, int sbo, float* red) {
   constexpr int NP = (Tile::EPI_PART > 0 && TSW / Tile::EPI_PART > 0) ? TSW / Tile::EPI_PART : 1;
-  if constexpr (NP == 1) {
+  if constexpr (PREDICT) {
+    // the same parts (each part's column sums enter cacc on their own)
+    if constexpr (NP == 1) {
+      fwd_tile_epilogue_predict_t<Tile, TSW>(p, c, acc, s0, s_own, sbo);
+    } else {
+      constexpr int H0 = TSW / NP, H = PART + 1 < NP ? H0 : TSW - (NP - 1) * H0;
+      f32x4 a[Tile::TL][H];
+#pragma unroll
+      for (int m = 0; m < Tile::TL; ++m)
+#pragma unroll
+        for (int n = 0; n < H; ++n) a[m][n] = acc[m][PART * H0 + n];
+      fwd_tile_epilogue_predict_t<Tile, H>(p, c, a, s0, s_own, sbo + PART * H0);
+      if constexpr (PART + 1 < NP)
+        fwd16_epilogue<Tile, TSW, PART + 1, true>(p, c, acc, s0, s_own, sbo, red);
+    }
+  } else if constexpr (NP == 1) {
     fwd_tile_epilogue_t<Tile, TSW>(p, c, acc, s0, s_own, sbo, red);
   } else {
     constexpr int H0 = TSW / NP, H = PART + 1 < NP ? H0 : TSW - (NP - 1) * H0;  // the last takes the rest
@@ -1143,7 +1344,7 @@ MPV_DEV void fwd16_epilogue(const FwdParams& p, const Fwd16Ctx c, f32x4 (&acc)[T
 // The s-tiles of one wave: TSW 16-sample blocks from sbo on, of every tile
 // the workgroup owns.  red_lds: the row-statistics exchange of the tiles that
 // keep it outside the ring.
-template <class Tile, int TSW>
+template <class Tile, int TSW, bool PREDICT = false>
 MPV_DEV void fwd16_tiles(const FwdParams& p, const Fwd16Ctx c, char* smem, float* red_lds,
                          typename Tile::Dma& dma, bool dmaw, int sbo) {
   constexpr int TL = Tile::TL, BM = Tile::BM;
@@ -1179,7 +1380,7 @@ MPV_DEV void fwd16_tiles(const FwdParams& p, const Fwd16Ctx c, char* smem, float
     float* red = Tile::RED_IN_RING
                      ? reinterpret_cast<float*>(smem + ((gs + kFwdRing - 1) % kFwdRing) * STAGE)
                      : red_lds;
-    fwd16_epilogue<Tile, TSW>(p, c, acc, s0, st * BM, sbo, red);
+    fwd16_epilogue<Tile, TSW, 0, PREDICT>(p, c, acc, s0, st * BM, sbo, red);
     // back to the K-loop priorities
     if (dmaw)
       __builtin_amdgcn_s_setprio(1);
@@ -1190,7 +1391,13 @@ MPV_DEV void fwd16_tiles(const FwdParams& p, const Fwd16Ctx c, char* smem, float
 
 // Every transposed 3xf16 tile (the descriptors above): 8 waves, 2-stage
 // LDS-DMA ring, one workgroup per CU.
-template <class Tile>
+// PREDICT (mpv_probit_predict): the same K loop, DMA ring and MFMA order with
+// the prediction epilogue; LDS loses the row-statistics exchange, half of
+// cacc and eight of the nine cols arrays, and is padded to kPredictLdsMin so
+// that the smaller kernel still runs one workgroup per CU (its packed fp32
+// epilogue beside another workgroup's waves is not used, see MPV_NO_PK_FP32).
+constexpr int kPredictLdsMin = 82 * 1024;
+template <class Tile, bool PREDICT = false>
 __global__ __launch_bounds__(kFwd16Threads, 1) void probit_fwd16_kernel(FwdParams p) {
   constexpr int WL = Tile::WL, WS = Tile::WS, TSA = Tile::TSA, TSB = Tile::TSB;
   constexpr int BM = Tile::BM, BN = Tile::BN;
@@ -1198,14 +1405,16 @@ __global__ __launch_bounds__(kFwd16Threads, 1) void probit_fwd16_kernel(FwdParam
                     BM == WS / 2 * (TSA + TSB) * 16 && (TSA == TSB || WS == 2),
                 "the descriptor's geometry");
   constexpr int STAGE = (BM + BN) * kRowB;
-  constexpr int RED = Tile::RED_IN_RING ? 0 : WL * BM * 6, CACC = WS * Tile::CQ * BN * 2;  // floats
+  constexpr int RED = (Tile::RED_IN_RING || PREDICT) ? 0 : WL * BM * 6,
+                CACC = WS * Tile::CQ * BN * (PREDICT ? 1 : 2);  // floats
   static_assert(!Tile::RED_IN_RING || WL * BM * 6 * 4 <= STAGE, "red fits one stage image");
-  constexpr int LDS = kFwdRing * STAGE + (RED + CACC + kColsT * BN) * 4;
-  __shared__ __attribute__((aligned(1024))) char smem[LDS > Tile::LDS_MIN ? LDS : Tile::LDS_MIN];
+  constexpr int LDS = kFwdRing * STAGE + (RED + CACC + (PREDICT ? 1 : kColsT) * BN) * 4;
+  constexpr int LDS_MIN = (PREDICT && Tile::LDS_MIN < kPredictLdsMin) ? kPredictLdsMin : Tile::LDS_MIN;
+  __shared__ __attribute__((aligned(1024))) char smem[LDS > LDS_MIN ? LDS : LDS_MIN];
   float* red = reinterpret_cast<float*>(smem + kFwdRing * STAGE);
   float* cacc = red + RED;
 
-  const Fwd16Ctx c = fwd16_ctx<Tile>(p, cacc, cacc + CACC);
+  const Fwd16Ctx c = fwd16_ctx<Tile, PREDICT>(p, cacc, cacc + CACC);
   const bool dmaw = c.wid >= 4;  // the second (TSB) half streams the stages
   typename Tile::Dma dma;
   dma.init(p, c.t_begin, c.b, c.n0, c.wid % 4, threadIdx.x & 63);
@@ -1217,12 +1426,53 @@ __global__ __launch_bounds__(kFwd16Threads, 1) void probit_fwd16_kernel(FwdParam
   // static priority (MI355X_MICROARCH.md, two waves per SIMD, item 4)
   if (dmaw) __builtin_amdgcn_s_setprio(1);
   if constexpr (TSA == TSB)
-    fwd16_tiles<Tile, TSA>(p, c, smem, red, dma, dmaw, c.ws * TSA);
+    fwd16_tiles<Tile, TSA, PREDICT>(p, c, smem, red, dma, dmaw, c.ws * TSA);
   else if (c.wid < 4)
-    fwd16_tiles<Tile, TSA>(p, c, smem, red, dma, false, 0);
+    fwd16_tiles<Tile, TSA, PREDICT>(p, c, smem, red, dma, false, 0);
   else
-    fwd16_tiles<Tile, TSB>(p, c, smem, red, dma, true, TSA);
-  fwd16t_colpart<WS * Tile::CQ, BN>(p, cacc, c.b, c.sc, c.n0);
+    fwd16_tiles<Tile, TSB, PREDICT>(p, c, smem, red, dma, true, TSA);
+  fwd16t_colpart<WS * Tile::CQ, BN, PREDICT>(p, cacc, c.b, c.sc, c.n0);
+}
+
+// After the prediction tiles (mpv_probit_predict): colsum (B, L) = the sum of
+// the nSc column partials (part != NULL) in the order the full forward sums
+// the same shape's -- chunk by chunk (fwd_combine's fold and sum_slabs_kernel),
+// or, `split`, sum_slabs_split_kernel's 16 strided groups added in order --
+// indiv_prob = colsum / S_total (write_indiv's division), and the device
+// Philox key's advance (as finalize_kernel).
+__global__ __launch_bounds__(256) void predict_final_kernel(const float* __restrict__ part, int nSc,
+                                                            int split, int64_t n,
+                                                            float* __restrict__ colsum,
+                                                            float* __restrict__ indiv,
+                                                            float S_total, uint64_t* seed_advance) {
+  if (seed_advance != nullptr && blockIdx.x == 0 && threadIdx.x == 0) *seed_advance += 1ull;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    float x;
+    if (part == nullptr) {
+      x = colsum[i];
+    } else {
+      if (split) {
+        float g[16];
+#pragma unroll
+        for (int j = 0; j < 16; ++j) g[j] = 0.0f;
+        for (int k0 = 0; k0 < nSc; k0 += 16) {
+#pragma unroll
+          for (int j = 0; j < 16; ++j)
+            if (k0 + j < nSc) g[j] += part[(int64_t)(k0 + j) * n + i];
+        }
+        x = g[0];
+#pragma unroll
+        for (int j = 1; j < 16; ++j) x += g[j];
+      } else {
+        x = 0.0f;
+#pragma unroll 8
+        for (int k = 0; k < nSc; ++k) x += part[(int64_t)k * n + i];
+      }
+      colsum[i] = x;
+    }
+    if (indiv != nullptr) indiv[i] = x / S_total;
+  }
 }
 
 // The six scalars of compute_loss (mpvae.py:147-148 KL, :188-190 nll, :122
@@ -1466,14 +1716,17 @@ __global__ __launch_bounds__(kFinalThreads) void finalize_kernel(mpv_final_args 
 struct FwdTile {
   int BM, BN, threads;
   void (*kernel)(FwdParams);
+  void (*predict)(FwdParams);  // the prediction variant (mpv_probit_predict)
 };
 template <class Tile>
 static FwdTile fwd16_tile() {
-  return {Tile::BM, Tile::BN, kFwd16Threads, probit_fwd16_kernel<Tile>};
+  return {Tile::BM, Tile::BN, kFwd16Threads, probit_fwd16_kernel<Tile>,
+          probit_fwd16_kernel<Tile, true>};
 }
 template <int WM, int WN, int TM, int TN>
 static FwdTile fwd32_tile() {
-  return {WM * TM * 16, WN * TN * 16, WM * WN * 64, probit_fwd_kernel<WM, WN, TM, TN>};
+  return {WM * TM * 16, WN * TN * 16, WM * WN * 64, probit_fwd_kernel<WM, WN, TM, TN>,
+          probit_fwd_kernel<WM, WN, TM, TN, true>};
 }
 
 // 48 labels (L <= 48), 96 labels (L <= 96), 128 labels (the transposed 3xf16
@@ -1579,6 +1832,79 @@ static int launch_finalize(const mpv_shape* shape, const mpv_final_args& a, int 
   return check_launch("finalize");
 }
 
+// The GEMM operands of a forward or prediction launch planned as `pl`.
+static int check_fwd_operands(const mpv_shape* shape, const FwdPlan& pl, int gemm, const float* R32,
+                              const float* eps, const mpv_split16& R16, const mpv_split16& eps16) {
+  if (gemm == MPV_GEMM_F32) {
+    MPV_REQUIRE(R32 && eps, "MPV_GEMM_F32 needs R32 and eps");
+  } else {
+    const int64_t ldk = 2 * cdiv(shape->z, kKC) * kKC;  // K slices the main loop reads
+    if (int rc = check_split_operand(R16, (int64_t)pl.nNt * pl.tile.BN, ldk, "R16")) return rc;
+    if (int rc = check_split_operand(eps16, shape->S_local * shape->B, ldk, "eps16")) return rc;
+    // the DMA issue keeps per-lane byte offsets within one s/l tile in 32 bits
+    MPV_REQUIRE((int64_t)pl.tile.BM * eps16.ld * 2 < (int64_t(1) << 32) &&
+                    (int64_t)pl.tile.BN * R16.ld * 2 < (int64_t(1) << 32),
+                "ld too large for the f16x3 tile offsets");
+  }
+  return MPV_OK;
+}
+
+// Bytes of the prediction's column partials [nSc][B][L] (0: the tiles write colsum).
+static size_t predict_colpart_bytes(const mpv_shape* s, const FwdPlan& pl) {
+  return pl.nSc > 1 ? align_up(sizeof(float) * (size_t)pl.nSc * s->B * s->L, 256) : 0;
+}
+
+static int run_predict(const mpv_shape* shape, const mpv_predict_args* a, void* stream) {
+  if (int rc = check_shape(shape)) return rc;
+  MPV_REQUIRE(a != nullptr, "args is NULL");
+  MPV_REQUIRE(a->fx_out && a->colsum, "NULL pointer in mpv_predict_args");
+  MPV_REQUIRE(a->gemm == MPV_GEMM_F32 || a->gemm == MPV_GEMM_F16X3, "unknown gemm mode %d",
+              a->gemm);
+  // the full forward's plan: the same tile, nSc and tps
+  const FwdPlan pl = plan_fwd(shape, a->gemm);
+  if (int rc = check_fwd_operands(shape, pl, a->gemm, a->R32, a->eps, a->R16, a->eps16)) return rc;
+  const size_t need = predict_colpart_bytes(shape, pl);
+  MPV_REQUIRE(need == 0 || (a->workspace && a->workspace_bytes >= need),
+              "workspace too small: %zu < %zu", a->workspace ? a->workspace_bytes : (size_t)0, need);
+  const int64_t blocks = (int64_t)shape->B * pl.nSc * pl.nNt;
+  MPV_REQUIRE(blocks < (int64_t(1) << 31), "grid too large");
+  hipStream_t st = as_stream(stream);
+  FwdParams p;
+  p.y = nullptr;
+  p.fe = nullptr;
+  p.fx = a->fx_out;
+  p.R = a->R32;
+  p.eps = a->eps;
+  p.R16 = a->R16;
+  p.eps16 = a->eps16;
+  p.T = nullptr;
+  p.rowpart = nullptr;
+  p.colpart = pl.nSc > 1 ? reinterpret_cast<float*>(a->workspace) : a->colsum;
+  p.S = (int)shape->S_local;
+  p.B = (int)shape->B;
+  p.L = (int)shape->L;
+  p.ldT = (int)t_cols(shape->L);
+  p.z = (int)shape->z;
+  p.nNt = pl.nNt;
+  p.nSc = pl.nSc;
+  p.tps = pl.tps;
+  p.nSt = pl.nSt;
+  MPV_LAUNCH("probit_predict", pl.tile.predict, dim3((unsigned)blocks), dim3(pl.tile.threads), 0,
+             st, p);
+  if (int rc = check_launch("probit_predict")) return rc;
+  if (pl.nSc == 1 && a->indiv_prob == nullptr && a->seed_advance == nullptr) return MPV_OK;
+  // The order of the full forward's sum of the same shape's partials: its
+  // buffer is (2, B, L), so launch_sum_slabs' split rule sees n = 2 B L.
+  const int64_t n = shape->B * shape->L;
+  const int split = pl.nSc > kCombineFoldSlabs && 2 * n <= 256 * 256;
+  int64_t nb = cdiv(n, 256);
+  if (nb > 2048) nb = 2048;
+  MPV_LAUNCH("predict_final", predict_final_kernel, dim3((unsigned)nb), dim3(256), 0, st,
+             pl.nSc > 1 ? p.colpart : nullptr, pl.nSc, split, n, a->colsum, a->indiv_prob,
+             (float)shape->S_total, a->seed_advance);
+  return check_launch("predict_final");
+}
+
 static int run_fwd(const mpv_shape* shape, const mpv_fwd_args* a, void* stream) {
   if (int rc = check_shape(shape)) return rc;
   MPV_REQUIRE(a != nullptr, "args is NULL");
@@ -1588,17 +1914,7 @@ static int run_fwd(const mpv_shape* shape, const mpv_fwd_args* a, void* stream) 
   MPV_REQUIRE(a->gemm == MPV_GEMM_F32 || a->gemm == MPV_GEMM_F16X3, "unknown gemm mode %d",
               a->gemm);
   const FwdPlan pl = plan_fwd(shape, a->gemm);
-  if (a->gemm == MPV_GEMM_F32) {
-    MPV_REQUIRE(a->R32 && a->eps, "MPV_GEMM_F32 needs R32 and eps");
-  } else {
-    const int64_t ldk = 2 * cdiv(shape->z, kKC) * kKC;  // K slices the main loop reads
-    if (int rc = check_split_operand(a->R16, (int64_t)pl.nNt * pl.tile.BN, ldk, "R16")) return rc;
-    if (int rc = check_split_operand(a->eps16, shape->S_local * shape->B, ldk, "eps16")) return rc;
-    // the DMA issue keeps per-lane byte offsets within one s/l tile in 32 bits
-    MPV_REQUIRE((int64_t)pl.tile.BM * a->eps16.ld * 2 < (int64_t(1) << 32) &&
-                    (int64_t)pl.tile.BN * a->R16.ld * 2 < (int64_t(1) << 32),
-                "ld too large for the f16x3 tile offsets");
-  }
+  if (int rc = check_fwd_operands(shape, pl, a->gemm, a->R32, a->eps, a->R16, a->eps16)) return rc;
   const size_t need = pl.rowpart_bytes + pl.colpart_bytes;
   MPV_REQUIRE(a->workspace_bytes >= need, "workspace too small: %zu < %zu", a->workspace_bytes,
               need);
@@ -1648,6 +1964,18 @@ extern "C" {
 
 int mpv_probit_fwd(const mpv_shape* shape, const mpv_fwd_args* a, void* stream) {
   return run_fwd(shape, a, stream);
+}
+
+size_t mpv_predict_workspace_bytes(const mpv_shape* shape) {
+  if (check_shape(shape) != MPV_OK) return 0;
+  size_t most = 0;  // enough for either GEMM mode's tiling
+  for (int gemm : {MPV_GEMM_F16X3, MPV_GEMM_F32})
+    most = std::max(most, predict_colpart_bytes(shape, plan_fwd(shape, gemm)));
+  return most;
+}
+
+int mpv_probit_predict(const mpv_shape* shape, const mpv_predict_args* a, void* stream) {
+  return run_predict(shape, a, stream);
 }
 
 int mpv_probit_finalize(const mpv_shape* shape, const mpv_final_args* a, void* stream) {

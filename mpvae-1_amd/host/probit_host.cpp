@@ -171,6 +171,31 @@ int mpvh_probit_fwd(const mpv_shape* shape, const mpvh_fwd_args* a) {
   return MPV_OK;
 }
 
+int mpvh_probit_predict(const mpv_shape* shape, const float* fx_out, const void* R, int R_dtype,
+                        const float* eps, double* colsum) {
+  if (int rc = check_shape(shape)) return rc;
+  REQ(fx_out && R && eps && colsum, "NULL pointer in mpvh_probit_predict");
+  REQ(R_dtype == MPV_F32 || R_dtype == MPV_F64, "unsupported R dtype %d", R_dtype);
+  const int64_t S = shape->S_local, B = shape->B, L = shape->L, z = shape->z;
+  const std::vector<double> Rd = r_as_f32(R, R_dtype, L * z);
+#pragma omp parallel
+  {
+    std::vector<float> t(L);
+    std::vector<double> cs(L);
+#pragma omp for schedule(dynamic, 1)
+    for (int64_t b = 0; b < B; ++b) {
+      const float* base = fx_out + b * L;
+      std::fill(cs.begin(), cs.end(), 0.0);
+      for (int64_t s = 0; s < S; ++s) {  // the samples in mpvh_probit_fwd's order
+        noise_product(eps + (s * B + b) * z, Rd.data(), L, z, t.data());
+        for (int64_t l = 0; l < L; ++l) cs[l] += static_cast<double>(probit_E(t[l] + base[l]));
+      }
+      std::copy(cs.begin(), cs.end(), colsum + b * L);
+    }
+  }
+  return MPV_OK;
+}
+
 int mpvh_bstat_combine(const double* g, int64_t R, int64_t B, double* out) {
   REQ(g && out && R > 0 && B > 0, "bad bstat_combine arguments");
   for (int64_t b = 0; b < B; ++b) {

@@ -8,6 +8,13 @@ Same public names, signatures, parameter names, shapes and dtypes:
                                        indiv_prob, indiv_prob_label)
                                   reference mpvae.py:145-210
 
+and one name the reference lacks:
+
+  predict_proba(fx_out, r_sqrt_sigma, args) -> indiv_prob
+                                  compute_loss(...)[6] alone, without labels
+                                  (mpvae.py:180, 203); VAE.predict_proba(feature,
+                                  args) runs the feature branch first
+
 Put ``mpvae-1_amd/`` on ``sys.path`` and ``from mpvae import VAE, compute_loss``
 works unchanged in the reference's training loop (fairsoft_train.py:57-146).
 The arithmetic runs in hand-written gfx950 kernels (libmpvae_hip.so),
@@ -42,9 +49,9 @@ import torch.nn.functional as F
 import mpvae_hip
 import mpvae_dist
 import mpvae_linear
-from mpvae_ops import ElboConfig, FusedReparam, ProbitELBO, SingleReparam
+from mpvae_ops import ElboConfig, FusedReparam, ProbitELBO, SingleReparam, probit_predict
 
-__all__ = ["VAE", "compute_loss"]
+__all__ = ["VAE", "compute_loss", "predict_proba"]
 
 # the encoders' dropout backward folded into mpv_linear (same values; False:
 # nn.Dropout's own backward kernel, for A/B)
@@ -208,6 +215,16 @@ class VAE(nn.Module):
             feat_out = self.feat_decode(torch.cat((feature, z_x), 1))
         return label_out, mu_e, lv_e, feat_out, mu_x, lv_x
 
+    def predict_proba(self, feature, args):
+        """indiv_prob (B, label_dim) of `feature` alone, without labels:
+        predict_proba(self.feat_forward(feature)[0], self.r_sqrt_sigma, args).
+
+        Only the feature encoder's dropouts and reparameterisation noise are
+        drawn; the reference's model(label, feat) draws the label encoder's
+        first, so under one seed the two see different feature-branch noise
+        (the same distribution).  No autograd."""
+        return predict_proba(self.feat_forward(feature)[0], self.r_sqrt_sigma, args)
+
 
 # Reference-exact CPU noise under sample sharding: every rank draws all
 # n_sample * B * z normals on its host (torch's CPU generator cannot skip ahead)
@@ -336,3 +353,43 @@ def compute_loss(input_label, fe_out, fe_mu, fe_logvar, fx_out, fx_mu, fx_logvar
                      backend=host_be, **kw)
     return ProbitELBO.apply(input_label.float(), fe_out, fe_mu, fe_logvar, fx_out, fx_mu,
                             fx_logvar, r_sqrt_sigma, noise, cfg)
+
+
+def predict_proba(fx_out, r_sqrt_sigma, args):
+    """indiv_prob = mean_s E_x (reference mpvae.py:180, 203), (B, label_dim)
+    float32, from the feature branch's probit mean ``fx_out`` (B, label_dim),
+    ``r_sqrt_sigma`` and the noise alone: no labels, no label branch, no loss
+    terms -- what the reference's evaluation and prediction extraction keep of
+    compute_loss (fairsoft_evaluate.py:70-81, fairsoft_prediction_extract.py:
+    62-67).  For the same inputs and noise the result equals
+    ``compute_loss(...)[6]`` bit for bit.
+
+    ``args`` is read exactly as compute_loss reads it: mode -> n_train_sample /
+    n_test_sample, z_dim, mpvae_noise (torch_cpu | philox | tensor), mpvae_seed,
+    mpvae_seed_advance, mpvae_gemm, mpvae_shard.  With torch_cpu noise it
+    consumes the same CPU generator draw as compute_loss, so it can replace
+    compute_loss in the reference's evaluation loop without moving the RNG
+    stream.  CUDA tensors run mpv_probit_predict, CPU tensors
+    mpvh_probit_predict; a mix raises.  With Philox noise and a device key it
+    is capturable in a HIP graph, as compute_loss is.
+
+    No autograd: the result has no grad_fn whatever the grad mode and whether
+    or not the inputs require gradients."""
+    host_be = _backend_for((fx_out, r_sqrt_sigma))
+    n_sample = args.n_train_sample if args.mode == "train" else args.n_test_sample
+    B, z = fx_out.shape[0], args.z_dim
+    if r_sqrt_sigma.dim() != 2 or r_sqrt_sigma.shape[1] != z:
+        raise ValueError(f"r_sqrt_sigma must be (label_dim, z_dim={z}), "
+                         f"got {tuple(r_sqrt_sigma.shape)}")
+    if n_sample <= 0:
+        raise IndexError(f"n_sample = {n_sample}: the Monte-Carlo sample axis is empty")
+    if fx_out.dim() != 2:
+        raise ValueError(f"fx_out must be (batch, label_dim), got {tuple(fx_out.shape)}")
+    if B == 0:
+        return torch.empty((0, fx_out.shape[1]), dtype=torch.float32, device=fx_out.device)
+    shard = mpvae_dist.shard_for(args, n_sample)
+    noise, kw = _noise_source(args, n_sample, B, z, shard, fx_out.device)
+    cfg = ElboConfig(n_sample, shard.S_local, shard.s_offset, 0.0, 0.0,
+                     exchange=shard.exchange, gemm=getattr(args, "mpvae_gemm", "f16x3"),
+                     backend=host_be, **kw)
+    return probit_predict(fx_out, r_sqrt_sigma, noise, cfg)

@@ -15,6 +15,8 @@ order) is:
             exp(m_r - M) (kernel mpv_bstat_combine).
   backward  one all_reduce(SUM) of the packed [d fe_out | d fx_out | d r_sqrt_sigma]
             buffer (the local backward kernels write straight into it).
+  predict   (predict_proba) one all_reduce(SUM) of the (B,L) sums of E_x over
+            s, then a plain division by n_sample.
 
 The MLP parameter gradients are then identical on every rank (they depend
 only on the reduced d fe_out / d fx_out / KL terms), so no DDP all-reduce is
@@ -139,9 +141,11 @@ class SampleShardExchange:
         dist.broadcast(t, src=self._src(), group=self.group)
         return int(t.item()) & (2 ** 64 - 1)
 
-    def verify_replicas(self, tensors):
+    def verify_replicas(self, tensors, names=None):
         """Raise ReplicaMismatch (on every rank) unless all ranks hold the same
-        tensors.  No-op unless this exchange was built with verify=True."""
+        tensors.  No-op unless this exchange was built with verify=True.
+        names: what the tensors are called in the message (default:
+        compute_loss's four)."""
         if not self.verify:
             return
         # compare bit patterns: a NaN checksum (NaN in a replica) or one of
@@ -152,9 +156,10 @@ class SampleShardExchange:
         dist.all_reduce(hi, op=dist.ReduceOp.MAX, group=self.group)
         if not torch.equal(lo, hi):
             bad = [i // 2 for i in range(ck.numel()) if int(lo[i]) != int(hi[i])]
-            names = ["input_label", "fe_out", "fx_out", "r_sqrt_sigma"]
+            what = "compute_loss" if names is None else "predict_proba"
+            names = list(names or ("input_label", "fe_out", "fx_out", "r_sqrt_sigma"))
             raise ReplicaMismatch(
-                "sample-sharded compute_loss: ranks hold different "
+                f"sample-sharded {what}: ranks hold different "
                 + ", ".join(sorted({names[i] if i < len(names) else str(i) for i in bad}))
                 + " -- seed torch and numpy identically on every rank (same batch, "
                   "dropout masks and reparameterisation draws)")
@@ -195,6 +200,13 @@ class SampleShardExchange:
                        lambda: dist.all_reduce(packed, group=self.group))
         B = bstat.shape[1]
         return packed[colsum.numel():].view(self.world, 6, B), colsum
+
+    def reduce_colsum(self, colsum):
+        """predict_proba: the ranks' (B, L) sums over their samples of E_x,
+        summed in place -- the prediction's one collective."""
+        COMM_TIMER.run("predict_all_reduce", colsum.device,
+                       lambda: dist.all_reduce(colsum, group=self.group))
+        return colsum
 
     def reduce_grads(self, flat):
         COMM_TIMER.run("reduce_grads", flat.device, lambda: dist.all_reduce(flat, group=self.group))

@@ -13,7 +13,7 @@ import torch  # noqa: F401  (must precede the .so load: one HIP runtime per proc
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MPVAE_HIP_LIB", os.path.join(HERE, "libmpvae_hip.so"))
 
-ABI_VERSION = 13
+ABI_VERSION = 14
 F32, F64 = 0, 1
 G_TOTAL, G_NLL, G_NLL_X, G_C, G_C_X, G_KL = range(6)
 
@@ -45,6 +45,13 @@ class FwdArgs(ctypes.Structure):
                 ("eps", vp), ("R16", Split16), ("eps16", Split16), ("T", vp), ("rowstat", vp),
                 ("bstat", vp), ("colsum", vp), ("workspace", vp),
                 ("workspace_bytes", ctypes.c_size_t)]
+
+
+class PredictArgs(ctypes.Structure):
+    """mpv_predict_args: the label-free prediction (mpv_probit_predict)."""
+    _fields_ = [("fx_out", vp), ("gemm", ctypes.c_int), ("R32", vp), ("eps", vp),
+                ("R16", Split16), ("eps16", Split16), ("colsum", vp), ("indiv_prob", vp),
+                ("seed_advance", vp), ("workspace", vp), ("workspace_bytes", ctypes.c_size_t)]
 
 
 class FinalArgs(ctypes.Structure):
@@ -184,6 +191,8 @@ SIGNATURES = {
                                                   ctypes.POINTER(Split16), vp]),
     "mpv_fwd_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Shape)]),
     "mpv_probit_fwd": (ctypes.c_int, [ctypes.POINTER(Shape), ctypes.POINTER(FwdArgs), vp]),
+    "mpv_predict_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Shape)]),
+    "mpv_probit_predict": (ctypes.c_int, [ctypes.POINTER(Shape), ctypes.POINTER(PredictArgs), vp]),
     "mpv_bstat_combine": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.c_int64, vp, vp]),
     "mpv_probit_finalize": (ctypes.c_int, [ctypes.POINTER(Shape), ctypes.POINTER(FinalArgs), vp]),
     "mpv_probit_finalize_shards": (ctypes.c_int, [ctypes.POINTER(Shape), vp, ctypes.c_int64, vp,
@@ -289,7 +298,8 @@ KERNELS = ["noise_philox", "split", "probit_fwd", "fwd_combine", "finalize", "bw
            "dR_gemm", "sum_slabs", "convert", "bstat_combine", "reparam_fwd", "reparam_bwd",
            "kl_bwd", "label_weights", "fair_fwd", "fair_bwd", "metrics", "linear", "adam",
            "adam_finish", "curve_keys", "curve_sort", "curve_merge", "curve_pass", "curve_agg",
-           "metric_sweep", "calib_fwd", "calib_tables", "calib_bwd"]
+           "metric_sweep", "calib_fwd", "calib_tables", "calib_bwd", "probit_predict",
+           "predict_final"]
 
 
 def kernel_times():

@@ -11,8 +11,9 @@ when it is missing.
 
 ``HostShardBackend`` has the per-shard interface of
 ``mpvae_ops.HipShardBackend`` (forward_local / combine_bstats / finalize /
-backward_local / kl_backward), so ``ProbitELBO`` and the sample-sharded exchange
-(mpvae_dist.py, gloo on CPU) drive it unchanged.
+backward_local / kl_backward / predict_local), so ``ProbitELBO``,
+``probit_predict`` and the sample-sharded exchange (mpvae_dist.py, gloo on CPU)
+drive it unchanged.
 """
 import ctypes
 import os
@@ -23,7 +24,7 @@ import mpvae_hip as H
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MPVAE_HOST_LIB", os.path.join(HERE, "libmpvae_host.so"))
-ABI_VERSION = 1
+ABI_VERSION = 2
 vp = ctypes.c_void_p
 F32, F64 = torch.float32, torch.float64
 
@@ -52,6 +53,7 @@ _SIGS = {
     "mpvh_last_error": (ctypes.c_char_p, []),
     "mpvh_set_threads": (ctypes.c_int, [ctypes.c_int]),
     "mpvh_probit_fwd": (ctypes.c_int, [ctypes.POINTER(H.Shape), ctypes.POINTER(FwdArgs)]),
+    "mpvh_probit_predict": (ctypes.c_int, [ctypes.POINTER(H.Shape), vp, vp, ctypes.c_int, vp, vp]),
     "mpvh_bstat_combine": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.c_int64, vp]),
     "mpvh_probit_finalize": (ctypes.c_int, [ctypes.POINTER(H.Shape), ctypes.POINTER(FinalArgs)]),
     "mpvh_probit_bwd": (ctypes.c_int, [ctypes.POINTER(H.Shape), ctypes.POINTER(BwdArgs)]),
@@ -136,6 +138,23 @@ class HostShardBackend:
                     _p(eps), _p(T), _p(rowstat), _p(bstat), _p(colsum))
         _check(load_library().mpvh_probit_fwd(shape, a), "mpvh_probit_fwd")
         return dict(rowstat=rowstat, bstat=bstat, colsum=colsum, T=T, packed=packed)
+
+    def predict_local(self, shape, fx_out, Rop, eps, want_indiv=True, seed_advance=None):
+        """mpvh_probit_predict: (this shard's (B, L) fp64 sum over s of E_x,
+        indiv_prob or None), the feature-branch half of forward_local."""
+        if seed_advance is not None:
+            raise ValueError("args.mpvae_seed_advance is a device-key option (philox on the GPU)")
+        colsum = torch.empty((shape.B, shape.L), dtype=F64)
+        fx_out = _c(fx_out, F32)
+        _check(load_library().mpvh_probit_predict(shape, _p(fx_out), _p(Rop),
+                                                  H.F64 if Rop.dtype == F64 else H.F32, _p(eps),
+                                                  _p(colsum)), "mpvh_probit_predict")
+        return colsum, (self.indiv_from_colsum(colsum, shape.S_total) if want_indiv else None)
+
+    @staticmethod
+    def indiv_from_colsum(colsum, S_total):
+        """mpvh_probit_finalize's indiv_prob: the fp64 quotient rounded to fp32."""
+        return (colsum / float(S_total)).to(F32)
 
     def combine_bstats(self, gathered):
         g = gathered.to(F64).contiguous()

@@ -231,6 +231,34 @@ class HipShardBackend:
         H.check(lib.mpv_probit_fwd(shape, args, H.stream_of(dev)), "mpv_probit_fwd")
         return dict(rowstat=rowstat, bstat=bstat, colsum=colsum, T=T, packed=packed)
 
+    def predict_local(self, shape, fx_out, Rop, eps, want_indiv=True, seed_advance=None):
+        """mpv_probit_predict: (this shard's (B, L) sum over s of E_x,
+        indiv_prob = that / S_total or None).  want_indiv=False for a sharded
+        caller, which divides after its all-reduce.  No host sync; the
+        workspace comes from the caching allocator (the graph pool inside a
+        capture)."""
+        lib = H.load_library()
+        dev = fx_out.device
+        B, L = shape.B, shape.L
+        colsum = self._buf((B, L), dev, torch.float32)
+        indiv = self._buf((B, L), dev, torch.float32) if want_indiv else None
+        nbytes = lib.mpv_predict_workspace_bytes(shape)
+        ws = self._buf((max(nbytes, 1),), dev, torch.uint8)
+        if self.gemm == H.GEMM_F16X3:
+            ops = (None, None, Rop.c(), eps.c())
+        else:
+            ops = (H.ptr(Rop), H.ptr(eps), H.Split16(), H.Split16())
+        args = H.PredictArgs(H.ptr(fx_out), self.gemm, *ops, H.ptr(colsum), H.ptr(indiv),
+                             H.ptr(seed_advance), H.ptr(ws), nbytes)
+        H.check(lib.mpv_probit_predict(shape, args, H.stream_of(dev)), "mpv_probit_predict")
+        return colsum, indiv
+
+    @staticmethod
+    def indiv_from_colsum(colsum, S_total):
+        """The all-reduced (B, L) column sums / S_total: a plain fp32 division
+        (by a device scalar; torch multiplies by the reciprocal of a host one)."""
+        return colsum / torch.full((), float(S_total), dtype=torch.float32, device=colsum.device)
+
     def _final_args(self, shape, bstat, colsum, fe_mu, fe_logvar, fx_mu, fx_logvar, nll_coeff,
                     c_coeff, seed_advance=None):
         dev = fe_mu.device
@@ -333,7 +361,7 @@ class LocalExchange:
     """Single shard: global statistics are the local ones."""
     world = 1
 
-    def verify_replicas(self, tensors):
+    def verify_replicas(self, tensors, names=None):
         pass
 
     def stat_slots(self):
@@ -361,6 +389,43 @@ class ElboConfig:
         # noise has read it (args.mpvae_seed_advance), or None
         self.seed_advance = seed_advance
         self.exchange = exchange if exchange is not None else LocalExchange()
+
+
+def probit_predict(fx_out, R, eps, cfg):
+    """indiv_prob = mean_s E_x (mpvae.py:180, 203) alone, with no labels, no
+    label branch and no loss terms: ProbitELBO.forward's noise and operand
+    preparation, then the backend's predict_local (mpv_probit_predict on the
+    GPU, mpvh_probit_predict for CPU tensors).  Sharded (cfg.exchange): one
+    all_reduce(SUM) of the (B, L) column sums, then a plain division by
+    S_total.  No autograd: the result never has a grad_fn."""
+    with torch.no_grad():
+        be = cfg.backend
+        fx_out = _f32(fx_out.detach(), "fx_out")
+        B, L = fx_out.shape
+        if R.dim() != 2 or R.shape[0] != L:
+            raise ValueError(f"r_sqrt_sigma must be (label_dim={L}, z_dim), got {tuple(R.shape)}")
+        R = R.detach()
+        z = R.shape[1]
+        cfg.exchange.verify_replicas((fx_out, R), names=("fx_out", "r_sqrt_sigma"))
+        shape = be.shape(cfg.S_local, cfg.S_total, cfg.s_offset, B, L, z)
+        if cfg.noise == "philox" and hasattr(be, "make_noise_and_R"):
+            eps, Rop = be.make_noise_and_R(shape, fx_out.device, cfg.seed, cfg.offset, R)
+        else:
+            if cfg.noise == "philox":
+                eps = be.make_noise(shape, fx_out.device, cfg.seed, cfg.offset)
+            else:
+                eps = _f32(eps, "noise")
+                if tuple(eps.shape) != (cfg.S_local, B, z):
+                    raise ValueError(f"noise must be {(cfg.S_local, B, z)}, "
+                                     f"got {tuple(eps.shape)}")
+                eps = be.prepare_noise(eps, shape)
+            Rop = be.prepare_R(R)
+        sharded = hasattr(cfg.exchange, "reduce_colsum")  # SampleShardExchange, not LocalExchange
+        colsum, indiv = be.predict_local(shape, fx_out, Rop, eps, want_indiv=not sharded,
+                                         seed_advance=cfg.seed_advance)
+        if sharded:
+            indiv = be.indiv_from_colsum(cfg.exchange.reduce_colsum(colsum), cfg.S_total)
+        return indiv
 
 
 class ProbitELBO(torch.autograd.Function):
