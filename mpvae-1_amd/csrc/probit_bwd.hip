@@ -11,12 +11,22 @@
 //                         + [y=0] betaN e^{5E} + g_indiv/S,
 //                    du = dE (1-1e-6) phi(u); column sums over s give d fe_out /
 //                    d fx_out; writes G = du + du_x (fp32 over T, or 3xf16 planes).
-//   dR16_kernel      dR[l][k] = sum_{s,b} G[s,b,l] eps[s,b,k], 3xf16 operands on
-//                    the f16 matrix cores; the rows (the K axis) are the LDS
+//                    bwd_elem_ring_kernel is the same pass through a per-wave
+//                    LDS ring (planes, more than 512 columns).  Shared:
+//                    elem_coef_load, d_elem2x4, poison_row, elem_colsum_store.
+//   dR16_kernel,     dR[l][k] = sum_{s,b} G[s,b,l] eps[s,b,k], 3xf16 operands on
+//   dR16s_kernel     the f16 matrix cores; the rows (the K axis) are the LDS
 //                    rows, fragments come from ds_read_b64_tr_b16 transposed
 //                    reads; split-K over the S*B rows into slabs reduced in a
-//                    fixed order (deterministic).
-//   dR_gemm_kernel   the same on exact fp32 MFMA (MPV_GEMM_F32).
+//                    fixed order (deterministic).  dR16_kernel takes the 64 and
+//                    128 tiles (L, z <= 64 / <= 128), dR16s_kernel, two wave
+//                    groups one phase apart, the 256 tile.
+//   dR_gemm_kernel   the same on exact fp32 MFMA (MPV_GEMM_F32), 128 tile.
+//                    Shared by the three: Dr16Tile (geometry), dr_ctx (what a
+//                    workgroup and its lanes own), dr_read + dr_mfma on a DrFrag
+//                    (3xf16), dr_store_slab.
+// Host: pick_dr_tile chooses the DrTile descriptor (edge, split-K target,
+// threads, kernel); plan_bwd derives the grids and the workspace layout from it.
 #include "abi_util.h"
 #include "mpv_common.h"
 
@@ -172,6 +182,16 @@ struct ElemCol {
                        // rkp = kp (-bP), rkn = kn bN carry them
 };
 
+// A degenerate row poisons every label, whatever its value (reference
+// autograd); rkp is NaN exactly when betaP is.
+MPV_DEV void poison_row(f32x2 (&out)[4], f32x2 rkp) {
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    if (rkp.x != rkp.x) out[q].x = rkp.x;
+    if (rkp.y != rkp.y) out[q].y = rkp.y;
+  }
+}
+
 // Four elements (columns) of one row at once, step-major so that the
 // dependent packed ops of one element interleave with the others'.
 // SOFT: the block may hold soft (non 0/1) labels (a per-column branch; false:
@@ -227,15 +247,7 @@ MPV_DEV void d_elem2x4(const float (&t)[4], const ElemCol& c, f32x2 alpha, f32x2
     dE = pk_fma(rk, f32x2{__builtin_amdgcn_exp2f(a.x), __builtin_amdgcn_exp2f(a.y)}, dE);
     out[q] = dE * ez[q];  // the coefficients carry kPhiK
   }
-  // a degenerate row poisons every label, whatever its value (reference autograd)
-  // (rkp is NaN exactly when betaP is)
-  if (NANCHK && (rkp.x != rkp.x || rkp.y != rkp.y)) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      if (rkp.x != rkp.x) out[q].x = rkp.x;
-      if (rkp.y != rkp.y) out[q].y = rkp.y;
-    }
-  }
+  if (NANCHK && (rkp.x != rkp.x || rkp.y != rkp.y)) poison_row(out, rkp);
 }
 
 // The ranking coefficients of one row from its betaP, betaN (label, feature).
@@ -251,13 +263,19 @@ struct ElemRow {
   float t[4];
 };
 
+// The six coefficients of sample row o = b*S + s (coef is [k][b][s]) as
+// (label, feature) pairs.
+MPV_DEV void elem_coef_load(const ElemParams& p, int64_t o, f32x2& alpha, f32x2& bP, f32x2& bN) {
+  const int64_t BS = (int64_t)p.B * p.S;
+  alpha = f32x2{p.coef[0 * BS + o], p.coef[3 * BS + o]};
+  bP = f32x2{p.coef[1 * BS + o], p.coef[4 * BS + o]};
+  bN = f32x2{p.coef[2 * BS + o], p.coef[5 * BS + o]};
+}
+
 MPV_DEV void elem_row_load(ElemRow& r, const ElemParams& p, int b, int s, int c0,
                            const bool (&ok)[4]) {
   const int64_t cb = (int64_t)b * p.S + s;
-  const int64_t BS = (int64_t)p.B * p.S;
-  r.alpha = f32x2{p.coef[0 * BS + cb], p.coef[3 * BS + cb]};
-  r.bP = f32x2{p.coef[1 * BS + cb], p.coef[4 * BS + cb]};
-  r.bN = f32x2{p.coef[2 * BS + cb], p.coef[5 * BS + cb]};
+  elem_coef_load(p, cb, r.alpha, r.bP, r.bN);
   const float* row = p.T + cb * p.ldT;
   if (c0 < p.L) {  // t_cols rows: the pad columns are readable
     // nontemporal T loads and G-plane stores: element pass -5 %
@@ -300,6 +318,33 @@ MPV_DEV void elem_col_setup(const ElemParams& p, int b, int c0, bool active, boo
   }
 }
 
+// Column sums of a block's rows -> colpart[sc][2][b][.]: every thread stages
+// its sg2 into cred (256 x 8 floats of LDS, free by now), then each of the
+// block's 4 TPR columns adds its RPI row-lanes in a fixed order.
+MPV_DEV void elem_colsum_store(const ElemParams& p, const f32x2 (&sg2)[4], float* cred, int TPR,
+                               int RPI) {
+  const int b = blockIdx.x, sc = blockIdx.y, tid = threadIdx.x;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    cred[tid * 8 + q] = sg2[q].x;
+    cred[tid * 8 + 4 + q] = sg2[q].y;
+  }
+  __syncthreads();
+  for (int j = tid; j < TPR * 4; j += blockDim.x) {
+    const int cqq = j >> 2, q = j & 3;
+    const int c = blockIdx.z * 1024 + j;
+    if (c < p.L) {
+      float e = 0.f, x = 0.f;
+      for (int r = 0; r < RPI; ++r) {
+        e += cred[(r * TPR + cqq) * 8 + q];
+        x += cred[(r * TPR + cqq) * 8 + 4 + q];
+      }
+      p.colpart[(((int64_t)sc * 2 + 0) * p.B + b) * p.L + c] = e;
+      p.colpart[(((int64_t)sc * 2 + 1) * p.B + b) * p.L + c] = x;
+    }
+  }
+}
+
 // Rows of T in flight per thread beyond the one computing (kElemLookahead).
 // The row index and the six per-row coefficients are per-lane (a block row
 // holds RPI rows of TPR threads), 12 more VGPRs than fit in 128: the kernel
@@ -316,7 +361,7 @@ __global__ __launch_bounds__(256, 3) void bwd_elem_kernel(ElemParams p) {
   const int rsub = tid / p.TPR, cq = tid % p.TPR;
   const bool active = rsub < p.RPI;
   const int c0 = blockIdx.z * 1024 + cq * 4;
-  const int S = p.S, B = p.B, L = p.L;
+  const int S = p.S, L = p.L;
   const float gs = PLANES ? wave_pow2_scale(p.g_bound, p.B) : 1.0f;
 
   bool ok[4];
@@ -374,26 +419,7 @@ __global__ __launch_bounds__(256, 3) void bwd_elem_kernel(ElemParams p) {
       for (int j = 0; j < LA; ++j) buf[j] = buf[j + 1];
     }
   }
-  // column sums over this block's rows: reduce the RPI row-lanes per column
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    cred[tid * 8 + q] = sg2[q].x;
-    cred[tid * 8 + 4 + q] = sg2[q].y;
-  }
-  __syncthreads();
-  for (int j = tid; j < p.TPR * 4; j += blockDim.x) {
-    const int cqq = j >> 2, q = j & 3;
-    const int c = blockIdx.z * 1024 + j;
-    if (c < L) {
-      float e = 0.f, x = 0.f;
-      for (int r = 0; r < p.RPI; ++r) {
-        e += cred[(r * p.TPR + cqq) * 8 + q];
-        x += cred[(r * p.TPR + cqq) * 8 + 4 + q];
-      }
-      p.colpart[(((int64_t)sc * 2 + 0) * B + b) * L + c] = e;
-      p.colpart[(((int64_t)sc * 2 + 1) * B + b) * L + c] = x;
-    }
-  }
+  elem_colsum_store(p, sg2, cred, p.TPR, p.RPI);
 }
 
 // The element pass for 3xf16 planes when one thread row of a block covers a
@@ -467,14 +493,9 @@ MPV_DEV void elem_ring_rows(const ElemParams& p, const ElemCol& ec, const bool (
       const f32x2 alpha = *reinterpret_cast<const f32x2*>(crow + rsel[0] + 8);
       d_elem2x4<SOFT, false, true>(t, ec, alpha, rkp, rkn, g2, rkq, &qc1);
     }
-    // a degenerate row poisons every label (the row's rkp is wave-uniform)
-    if (NANCHK && __builtin_amdgcn_readfirstlane((rkp.x != rkp.x || rkp.y != rkp.y) ? 1 : 0)) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        if (rkp.x != rkp.x) g2[q].x = rkp.x;
-        if (rkp.y != rkp.y) g2[q].y = rkp.y;
-      }
-    }
+    // (the row's rkp is wave-uniform)
+    if (NANCHK && __builtin_amdgcn_readfirstlane((rkp.x != rkp.x || rkp.y != rkp.y) ? 1 : 0))
+      poison_row(g2, rkp);
     float G[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -552,22 +573,18 @@ __global__ __launch_bounds__(256, 3) void bwd_elem_ring_kernel(ElemParams p) {
   const bool live = c0 < p.Lc;
   const int s_begin = sc * p.rows_per_chunk;
   const int s_end = min(S, s_begin + p.rows_per_chunk);
-  const int64_t BS = (int64_t)B * S;
   // lanes past the row's end (L % 1024 != 0) re-read column 0 and are masked
   const uint32_t voff = (uint32_t)((c0 < L ? c0 : 0) * 4);
   f32x2 sg2[4] = {splat2(0.f), splat2(0.f), splat2(0.f), splat2(0.f)};
   for (int sb = s_begin; sb < s_end; sb += CR) {  // sub-chunks of <= CR rows
     const int nrows = min(CR, s_end - sb);
     __syncthreads();  // the previous sub-chunk's cf reads are done
-    // coef is [k][b][s]: cf[row] = rkp, alpha, rkn, alpha as (label, feature)
-    // pairs (alpha 8 bytes past either ranking coefficient: elem_ring_rows)
+    // cf[row] = rkp, alpha, rkn, alpha as (label, feature) pairs (alpha 8
+    // bytes past either ranking coefficient: elem_ring_rows)
     bool nan_row = false;
     for (int r = tid; r < nrows; r += 256) {
-      const int64_t o = (int64_t)b * S + sb + r;
-      const f32x2 alpha{p.coef[o], p.coef[3 * BS + o]};
-      const f32x2 bP{p.coef[BS + o], p.coef[4 * BS + o]};
-      const f32x2 bN{p.coef[2 * BS + o], p.coef[5 * BS + o]};
-      f32x2 rkp, rkn;
+      f32x2 alpha, bP, bN, rkp, rkn;
+      elem_coef_load(p, (int64_t)b * S + sb + r, alpha, bP, bN);
       elem_rank_coefs(ec, bP, bN, rkp, rkn);
       nan_row |= bP.x != bP.x || bP.y != bP.y;
       *reinterpret_cast<f32x4*>(&cf[r][0]) = f32x4{rkp.x, rkp.y, alpha.x, alpha.y};
@@ -586,23 +603,18 @@ __global__ __launch_bounds__(256, 3) void bwd_elem_ring_kernel(ElemParams p) {
                                           sg2);
     }
   }
-  // column sums of the block's rows -> colpart (the ring is free now)
+  // the ring is free now: its first 8 KB serve as cred
   __syncthreads();
-  float* cred = &ring[0][0][0];  // 256 x 8 floats (8 KB, within the ring)
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    cred[tid * 8 + q] = sg2[q].x;
-    cred[tid * 8 + 4 + q] = sg2[q].y;
-  }
-  __syncthreads();
-  for (int j = tid; j < 1024; j += 256) {
-    const int c = blockIdx.z * 1024 + j;
-    if (c < L) {
-      p.colpart[(((int64_t)sc * 2 + 0) * B + b) * L + c] = cred[(j >> 2) * 8 + (j & 3)];
-      p.colpart[(((int64_t)sc * 2 + 1) * B + b) * L + c] = cred[(j >> 2) * 8 + 4 + (j & 3)];
-    }
-  }
+  elem_colsum_store(p, sg2, &ring[0][0][0], 256, 1);
 }
+
+// ---------------------------------------------------------------- dR GEMMs
+// What every dR GEMM kernel (3xf16 or fp32) takes: the split-K grid and its output.
+struct DrCommon {
+  float* slab;  // [nKc][L][z]
+  int S, B, L, z;
+  int nLt, nZt, nKc, rows_per_chunk;
+};
 
 // ------------------------------------------------------------ 3xf16 dR GEMM
 // K axis = the S*B sample rows q = b*S + s: the noise planes' own row order, in
@@ -619,19 +631,37 @@ __global__ __launch_bounds__(256, 3) void bwd_elem_ring_kernel(ElemParams p) {
 // positions mod 256 B, all 64 banks once: conflict-free (checked).
 // Element j of lane group g holds K row (j < 4 ? 4g + j : 16 + 4g + j - 4), the
 // same for A and B.
+// (k sits where its fields always were: the kernels' argument layout is unchanged)
 struct Dr16Params {
   const uint16_t* g;    // chunked G planes, rows b*S + s, gld halves per row
   const float* g_bound;  // (B) per-row bounds of |G|: the planes' scale (wave_pow2_scale)
   int64_t gld;
   mpv_split16 eps16;    // rows b*S + s
-  float* slab;          // [nKc][L][z]
-  int S, B, L, z;
-  int nLt, nZt, nKc, rows_per_chunk, rows_pad;
+  DrCommon k;
+  int rows_pad;
 };
 
 constexpr int kDrKR = 32;     // K rows per stage (one MFMA k-step)
 
-MPV_DEV s16x4 tr_read(const char* base, int off) {
+// Geometry of a 3xf16 dR tile: WM x WN waves, each TM x TN MFMA tiles of 16 x 16.
+template <int WM_, int WN_, int TM_, int TN_>
+struct Dr16Tile {
+  static constexpr int WM = WM_, WN = WN_, TM = TM_, TN = TN_;
+  static constexpr int NW = WM * WN;
+  static constexpr int BL = WM * TM * 16, BZ = WN * TN * 16;
+  static_assert(BL == BZ, "square tile: one LDS row layout for both operands");
+  static constexpr int ROWB = BL * 4;          // bytes per LDS row: BL columns, hi + lo
+  static constexpr int IMG = kDrKR * ROWB;     // per operand
+  static constexpr int STAGE = 2 * IMG;
+  static constexpr int PIECES = STAGE / 1024;  // 1-KB wave-instructions per stage
+  static constexpr int RPP = 1024 / ROWB;      // rows per piece
+  static_assert(RPP >= 1 && RPP * ROWB == 1024, "a 1-KB DMA piece is whole rows");
+};
+
+// base: a generic pointer into LDS or an LDS-typed one (lds_cptr)
+using lds_cptr = const __attribute__((address_space(3))) char*;
+template <class Ptr>
+MPV_DEV s16x4 tr_read(Ptr base, int off) {
   return __builtin_amdgcn_ds_read_tr16_b64_v4i16(
       (__attribute__((address_space(3))) s16x4*)(base + off));
 }
@@ -648,6 +678,106 @@ MPV_DEV void decode_kc_tile(int id, int K, int nT, int& kc, int& tile) {
     tile = r / Kr;
     kc = (K / 8) * 8 + (r % Kr);
   }
+}
+
+// What a dR workgroup and its waves and lanes own, fixed for its life.
+struct DrCtx {
+  int kc, tile, l0, z0;      // K chunk, output tile and its first label / latent column
+  int wid, wm, wn;           // wave (uniform) and its place in the WM x WN grid
+  int lane, lr, lg;          // lane, lane & 15, lane >> 4
+  int rows;                  // sample rows B*S
+  int q_begin, q_end;        // the chunk's K rows
+  int r0, r1, sw, tp;        // transposed reads: the lane's two LDS rows, r0 & 7, 16-B part
+};
+
+// q_limit: where the last chunk ends (the 3xf16 kernels run over the padded rows).
+template <int BL, int BZ, int WN>
+MPV_DEV DrCtx dr_ctx(const DrCommon& p, int q_limit) {
+  DrCtx c;
+  decode_kc_tile(blockIdx.x, p.nKc, p.nLt * p.nZt, c.kc, c.tile);
+  c.l0 = (c.tile / p.nZt) * BL, c.z0 = (c.tile % p.nZt) * BZ;
+  c.lane = threadIdx.x & 63;
+  c.wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  c.wm = c.wid / WN, c.wn = c.wid % WN;
+  c.lr = c.lane & 15, c.lg = c.lane >> 4;
+  c.rows = p.B * p.S;
+  c.q_begin = c.kc * p.rows_per_chunk;
+  c.q_end = min(q_limit, c.q_begin + p.rows_per_chunk);
+  // lane 4q+p of its 16-lane group
+  const int tq = c.lr >> 2;
+  c.tp = c.lr & 3;
+  c.r0 = c.lg * 4 + tq, c.r1 = c.r0 + 16, c.sw = c.r0 & 7;
+  return c;
+}
+
+// The workgroup's tile of slab kc.  D[i = l][j = z]: row = lg*4 + reg, col = lr.
+// SCALED false (fp32 operands): the accumulators as they are.
+template <bool SCALED = true, int TM, int TN>
+MPV_DEV void dr_store_slab(const f32x4 (&acc)[TM][TN], const DrCtx& c, const DrCommon& k,
+                           float inv = 1.0f) {
+  const int L = k.L, z = k.z;
+#pragma unroll
+  for (int m = 0; m < TM; ++m)
+#pragma unroll
+    for (int n = 0; n < TN; ++n)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int l = c.l0 + (c.wm * TM + m) * 16 + c.lg * 4 + i;
+        const int zc = c.z0 + (c.wn * TN + n) * 16 + c.lr;
+        if (l < L && zc < z)
+          k.slab[((int64_t)c.kc * L + l) * z + zc] = SCALED ? acc[m][n][i] * inv : acc[m][n][i];
+      }
+}
+
+// 1 / (the G planes' scale x the noise planes' scale): the 3xf16 slabs' factor
+MPV_DEV float dr16_inv_scale(const Dr16Params& p) {
+  return 1.0f / (wave_pow2_scale(p.g_bound, p.k.B) * *p.eps16.scale);
+}
+
+// Fragments of one dR stage (per wave: TM A tiles and TN B tiles, hi and lo).
+template <int TM, int TN>
+struct DrFrag {
+  s16x8 ah[TM], al[TM], bh[TN], bl[TN];
+};
+
+template <class T, class Ptr>
+MPV_DEV void dr_read(DrFrag<T::TM, T::TN>& f, Ptr base, const DrCtx& c) {
+  constexpr int TM = T::TM, TN = T::TN, ROWB = T::ROWB, IMG = T::IMG;
+  const int r0 = c.r0, r1 = c.r1, sw = c.sw, tp = c.tp;
+#pragma unroll
+  for (int m = 0; m < TM; ++m) {
+    const int t = c.wm * TM + m, uh = (t >> 1) * 4 + (t & 1);
+    const int ch = ((uh ^ sw) << 5) + tp * 8, cl = (((uh + 2) ^ sw) << 5) + tp * 8;
+    f.ah[m] = __builtin_shufflevector(tr_read(base, r0 * ROWB + ch), tr_read(base, r1 * ROWB + ch),
+                                      0, 1, 2, 3, 4, 5, 6, 7);
+    f.al[m] = __builtin_shufflevector(tr_read(base, r0 * ROWB + cl), tr_read(base, r1 * ROWB + cl),
+                                      0, 1, 2, 3, 4, 5, 6, 7);
+  }
+#pragma unroll
+  for (int n = 0; n < TN; ++n) {
+    const int t = c.wn * TN + n, uh = (t >> 1) * 4 + (t & 1);
+    const int ch = ((uh ^ sw) << 5) + tp * 8, cl = (((uh + 2) ^ sw) << 5) + tp * 8;
+    f.bh[n] = __builtin_shufflevector(tr_read(base + IMG, r0 * ROWB + ch),
+                                      tr_read(base + IMG, r1 * ROWB + ch), 0, 1, 2, 3, 4, 5, 6, 7);
+    f.bl[n] = __builtin_shufflevector(tr_read(base + IMG, r0 * ROWB + cl),
+                                      tr_read(base + IMG, r1 * ROWB + cl), 0, 1, 2, 3, 4, 5, 6, 7);
+  }
+}
+
+// The stage's 3xf16 products: hi hi, hi lo, lo hi.
+template <int TM, int TN>
+MPV_DEV void dr_mfma(f32x4 (&acc)[TM][TN], const DrFrag<TM, TN>& f) {
+#pragma unroll
+  for (int m = 0; m < TM; ++m)
+#pragma unroll
+    for (int n = 0; n < TN; ++n) {
+      acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(as_f16x8(f.ah[m]), as_f16x8(f.bh[n]),
+                                                         acc[m][n], 0, 0, 0);
+      acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(as_f16x8(f.ah[m]), as_f16x8(f.bl[n]),
+                                                         acc[m][n], 0, 0, 0);
+      acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(as_f16x8(f.al[m]), as_f16x8(f.bh[n]),
+                                                         acc[m][n], 0, 0, 0);
+    }
 }
 
 // One stage's LDS-DMA for this wave: PER_WAVE 1-KB pieces of RPP whole rows.
@@ -676,141 +806,64 @@ MPV_DEV void dr_issue(const Dr16Params& p, char* dst, int q0, int rows, int wid,
   }
 }
 
-template <int WM, int WN, int TM, int TN, int kDrStages>
+// The 64 and 128 tiles: every wave streams its share of stage ci+1 (a burst of
+// LDS-DMA) and then reads and multiplies stage ci; two stage images, one
+// barrier per stage.
+template <int WM, int WN, int TM, int TN>
 __global__ __launch_bounds__(WM* WN * 64, 1) void dR16_kernel(Dr16Params p) {
-  constexpr int NW = WM * WN;
-  constexpr int BL = WM * TM * 16, BZ = WN * TN * 16;
-  static_assert(BL == BZ, "square tile: one LDS row layout for both operands");
-  constexpr int ROWB = BL * 4;          // bytes per LDS row: BL columns, hi + lo
-  constexpr int IMG = kDrKR * ROWB;     // per operand
-  constexpr int STAGE = 2 * IMG;
-  constexpr int PIECES = STAGE / 1024;  // 1-KB wave-instructions per stage
-  constexpr int RPP = 1024 / ROWB;      // rows per piece
-  static_assert(PIECES % NW == 0, "DMA pieces must split over waves");
-  constexpr int PER_WAVE = PIECES / NW;
-  constexpr int P = kDrStages - 1;
-  __shared__ __attribute__((aligned(1024))) char smem[kDrStages * STAGE];
+  using T = Dr16Tile<WM, WN, TM, TN>;
+  constexpr int STAGE = T::STAGE, PIECES = T::PIECES, RPP = T::RPP;
+  static_assert(PIECES % T::NW == 0, "DMA pieces must split over waves");
+  constexpr int PER_WAVE = PIECES / T::NW;
+  __shared__ __attribute__((aligned(1024))) char smem[2 * STAGE];
 
-  int kc, tile;
-  decode_kc_tile(blockIdx.x, p.nKc, p.nLt * p.nZt, kc, tile);
-  const int l0 = (tile / p.nZt) * BL, z0 = (tile % p.nZt) * BZ;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wid / WN, wn = wid % WN;
-  const int lr = lane & 15, lg = lane >> 4;
-  const int rows = p.B * p.S;
-  const int q_begin = kc * p.rows_per_chunk;
-  const int q_end = min(p.rows_pad, q_begin + p.rows_per_chunk);
+  const DrCtx c = dr_ctx<T::BL, T::BZ, WN>(p.k, p.rows_pad);
   // DMA lane mapping: RPP rows per 1-KB wave-instruction; wave w moves pieces
   // w*PER_WAVE ..; the first PIECES/2 are G rows, the rest E rows.  Per-lane
   // byte offsets (without the stage's first row) of my pieces:
   int dma_off[PER_WAVE];
 #pragma unroll
   for (int i = 0; i < PER_WAVE; ++i) {
-    const int pc = wid * PER_WAVE + i;
+    const int pc = c.wid * PER_WAVE + i;
     const int pr = pc % (PIECES / 2);
-    const int lrow = lane / (64 / RPP), lpos = lane % (64 / RPP);  // 16-B slot within the row
+    const int lrow = c.lane / (64 / RPP), lpos = c.lane % (64 / RPP);  // 16-B slot within the row
     const int r = pr * RPP + lrow;  // K row within the stage
     const int u_lds = lpos >> 1, half = lpos & 1;
     const int u_src = u_lds ^ (r & 7);
-    dma_off[i] = 4 * (pc < PIECES / 2 ? l0 : z0) + u_src * 32 + half * 16;  // chunked: 4 B/column
+    // (chunked planes: 4 B per column)
+    dma_off[i] = 4 * (pc < PIECES / 2 ? c.l0 : c.z0) + u_src * 32 + half * 16;
   }
-  // transposed-read lane mapping: lane 4q+p of its 16-lane group
-  const int tq = lr >> 2, tp = lr & 3;
-  const int r0 = lg * 4 + tq, r1 = r0 + 16, sw = r0 & 7;
 
+  // (The zeroing loops and the stage count stay written out here and in
+  // dR16s_kernel, in this order: with the count a DrCtx field, the accumulators
+  // zeroed by an initialiser, or both in a helper, hipcc allocates
+  // dR16s_kernel's registers differently and it runs 1.4-2 % slower at C4.)
   f32x4 acc[TM][TN];
 #pragma unroll
   for (int m = 0; m < TM; ++m)
 #pragma unroll
     for (int n = 0; n < TN; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  const int nst = (q_end - q_begin + kDrKR - 1) / kDrKR;
-  for (int j = 0; j < P && j < nst; ++j)
-    dr_issue<PER_WAVE, PIECES, RPP>(p, smem + j * STAGE, q_begin + j * kDrKR, rows, wid, dma_off);
+  const int nst = (c.q_end - c.q_begin + kDrKR - 1) / kDrKR;
+  // (a loop of one pass, not an if: after an if hipcc waits for all of a
+  // stage's fragment reads before its first MFMA instead of read by read)
+  for (int j = 0; j < 1 && j < nst; ++j)
+    dr_issue<PER_WAVE, PIECES, RPP>(p, smem + j * STAGE, c.q_begin + j * kDrKR, c.rows, c.wid,
+                                    dma_off);
   for (int ci = 0; ci < nst; ++ci) {
-    if (P == 1)
-      wait_vmcnt<0>();
-    else
-      wait_vmcnt_dyn(min(P - 1, nst - 1 - ci) * PER_WAVE);
+    wait_vmcnt<0>();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     barrier_raw();  // stage ci landed for every wave; all waves are done reading ci-1
-    if (ci + P < nst)
-      dr_issue<PER_WAVE, PIECES, RPP>(p, smem + ((ci + P) % kDrStages) * STAGE,
-                                 q_begin + (ci + P) * kDrKR, rows, wid, dma_off);
-    const char* base = smem + (ci % kDrStages) * STAGE;
-    s16x8 ah[TM], al[TM], bh[TN], bl[TN];
-#pragma unroll
-    for (int m = 0; m < TM; ++m) {
-      const int t = wm * TM + m, uh = (t >> 1) * 4 + (t & 1);
-      const int ch = ((uh ^ sw) << 5) + tp * 8, cl = (((uh + 2) ^ sw) << 5) + tp * 8;
-      ah[m] = __builtin_shufflevector(tr_read(base, r0 * ROWB + ch),
-                                      tr_read(base, r1 * ROWB + ch), 0, 1, 2, 3, 4, 5, 6, 7);
-      al[m] = __builtin_shufflevector(tr_read(base, r0 * ROWB + cl),
-                                      tr_read(base, r1 * ROWB + cl), 0, 1, 2, 3, 4, 5, 6, 7);
-    }
-#pragma unroll
-    for (int n = 0; n < TN; ++n) {
-      const int t = wn * TN + n, uh = (t >> 1) * 4 + (t & 1);
-      const int ch = ((uh ^ sw) << 5) + tp * 8, cl = (((uh + 2) ^ sw) << 5) + tp * 8;
-      bh[n] = __builtin_shufflevector(tr_read(base + IMG, r0 * ROWB + ch),
-                                      tr_read(base + IMG, r1 * ROWB + ch), 0, 1, 2, 3, 4, 5, 6, 7);
-      bl[n] = __builtin_shufflevector(tr_read(base + IMG, r0 * ROWB + cl),
-                                      tr_read(base + IMG, r1 * ROWB + cl), 0, 1, 2, 3, 4, 5, 6, 7);
-    }
-#pragma unroll
-    for (int m = 0; m < TM; ++m)
-#pragma unroll
-      for (int n = 0; n < TN; ++n) {
-        acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(as_f16x8(ah[m]), as_f16x8(bh[n]),
-                                                           acc[m][n], 0, 0, 0);
-        acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(as_f16x8(ah[m]), as_f16x8(bl[n]),
-                                                           acc[m][n], 0, 0, 0);
-        acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(as_f16x8(al[m]), as_f16x8(bh[n]),
-                                                           acc[m][n], 0, 0, 0);
-      }
+    if (ci + 1 < nst)
+      dr_issue<PER_WAVE, PIECES, RPP>(p, smem + ((ci + 1) % 2) * STAGE,
+                                      c.q_begin + (ci + 1) * kDrKR, c.rows, c.wid, dma_off);
+    DrFrag<TM, TN> f;
+    // (an LDS-typed base: through the generic pointer dR16s_kernel still passes,
+    // hipcc here adds the lane's row offset again at every read, 15 more VALU
+    // instructions per stage of the 128 tile)
+    dr_read<T>(f, (lds_cptr)(smem + (ci % 2) * STAGE), c);
+    dr_mfma(acc, f);
   }
-  const float inv = 1.0f / (wave_pow2_scale(p.g_bound, p.B) * *p.eps16.scale);
-  // D[i = l][j = z]: row = lg*4 + reg, col = lr
-#pragma unroll
-  for (int m = 0; m < TM; ++m)
-#pragma unroll
-    for (int n = 0; n < TN; ++n)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int l = l0 + (wm * TM + m) * 16 + lg * 4 + i;
-        const int zc = z0 + (wn * TN + n) * 16 + lr;
-        if (l < p.L && zc < p.z) p.slab[((int64_t)kc * p.L + l) * p.z + zc] = acc[m][n][i] * inv;
-      }
-}
-
-// Fragments of one dR stage (per wave: TM A tiles and TN B tiles, hi and lo).
-template <int TM, int TN>
-struct DrFrag {
-  s16x8 ah[TM], al[TM], bh[TN], bl[TN];
-};
-
-template <int TM, int TN, int ROWB, int IMG>
-MPV_DEV void dr_read(DrFrag<TM, TN>& f, const char* base, int wm, int wn, int r0, int r1, int sw,
-                     int tp) {
-#pragma unroll
-  for (int m = 0; m < TM; ++m) {
-    const int t = wm * TM + m, uh = (t >> 1) * 4 + (t & 1);
-    const int ch = ((uh ^ sw) << 5) + tp * 8, cl = (((uh + 2) ^ sw) << 5) + tp * 8;
-    f.ah[m] = __builtin_shufflevector(tr_read(base, r0 * ROWB + ch), tr_read(base, r1 * ROWB + ch),
-                                      0, 1, 2, 3, 4, 5, 6, 7);
-    f.al[m] = __builtin_shufflevector(tr_read(base, r0 * ROWB + cl), tr_read(base, r1 * ROWB + cl),
-                                      0, 1, 2, 3, 4, 5, 6, 7);
-  }
-#pragma unroll
-  for (int n = 0; n < TN; ++n) {
-    const int t = wn * TN + n, uh = (t >> 1) * 4 + (t & 1);
-    const int ch = ((uh ^ sw) << 5) + tp * 8, cl = (((uh + 2) ^ sw) << 5) + tp * 8;
-    f.bh[n] = __builtin_shufflevector(tr_read(base + IMG, r0 * ROWB + ch),
-                                      tr_read(base + IMG, r1 * ROWB + ch), 0, 1, 2, 3, 4, 5, 6, 7);
-    f.bl[n] = __builtin_shufflevector(tr_read(base + IMG, r0 * ROWB + cl),
-                                      tr_read(base + IMG, r1 * ROWB + cl), 0, 1, 2, 3, 4, 5, 6, 7);
-  }
+  dr_store_slab(acc, c, p.k, dr16_inv_scale(p));
 }
 
 // dr_read with a group-0 wave's share of the next stage's LDS-DMA woven in:
@@ -820,10 +873,11 @@ MPV_DEV void dr_read(DrFrag<TM, TN>& f, const char* base, int wm, int wn, int r0
 // issue 1060 + reads 960 ticks, serial, against 1650 for the other group's
 // MFMAs).  Noise rows past the last real one (a padded last stage) repeat
 // that row, as drs_issue_range clamps them.
-template <int TM, int TN, int ROWB, int IMG, int PER_WAVE, class Dma>
-MPV_DEV void dr_read_dma(DrFrag<TM, TN>& f, const char* base, int wm, int wn, int r0, int r1,
-                         int sw, int tp, Dma& dma, char* dst, int rows, int lane_u, int lane_h) {
-  constexpr int STEPS = TM + TN;
+template <class T, int PER_WAVE, class Dma>
+MPV_DEV void dr_read_dma(DrFrag<T::TM, T::TN>& f, const char* base, const DrCtx& c, Dma& dma,
+                         char* dst, int lane_u, int lane_h) {
+  constexpr int TM = T::TM, TN = T::TN, ROWB = T::ROWB, IMG = T::IMG, STEPS = TM + TN;
+  const int wm = c.wm, wn = c.wn, r0 = c.r0, r1 = c.r1, sw = c.sw, tp = c.tp, rows = c.rows;
   // the per-piece source swizzle is recomputed next to its DMA, not hoisted
   // out of the stage loop (8 more live VGPRs spill the accumulators)
   int lu = lane_u;
@@ -861,21 +915,6 @@ MPV_DEV void dr_read_dma(DrFrag<TM, TN>& f, const char* base, int wm, int wn, in
     __builtin_amdgcn_sched_barrier(0);
   }
   dma.end();
-}
-
-template <int TM, int TN>
-MPV_DEV void dr_mfma(f32x4 (&acc)[TM][TN], const DrFrag<TM, TN>& f) {
-#pragma unroll
-  for (int m = 0; m < TM; ++m)
-#pragma unroll
-    for (int n = 0; n < TN; ++n) {
-      acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(as_f16x8(f.ah[m]), as_f16x8(f.bh[n]),
-                                                         acc[m][n], 0, 0, 0);
-      acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(as_f16x8(f.ah[m]), as_f16x8(f.bl[n]),
-                                                         acc[m][n], 0, 0, 0);
-      acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(as_f16x8(f.al[m]), as_f16x8(f.bh[n]),
-                                                         acc[m][n], 0, 0, 0);
-    }
 }
 
 // Pieces pc0 .. pc0+COUNT-1 of one stage's LDS-DMA (one row each: the first
@@ -946,50 +985,34 @@ struct DrsDma {
 template <int WM, int WN, int TM, int TN>
 __global__ __launch_bounds__(WM* WN * 64, 1) void dR16s_kernel(Dr16Params p) {
   static_assert(WM == 2, "two wave groups");
-  constexpr int BL = WM * TM * 16, BZ = WN * TN * 16;
-  static_assert(BL == BZ, "square tile: one LDS row layout for both operands");
-  constexpr int ROWB = BL * 4;          // bytes per LDS row: BL columns, hi + lo
-  constexpr int IMG = kDrKR * ROWB;     // per operand
-  constexpr int STAGE = 2 * IMG;
-  constexpr int PIECES = STAGE / 1024;  // 1-KB wave-instructions per stage
-  constexpr int RPP = 1024 / ROWB;      // rows per piece
+  using T = Dr16Tile<WM, WN, TM, TN>;
+  constexpr int STAGE = T::STAGE, PIECES = T::PIECES;
   constexpr int PER_WAVE = PIECES / WN;  // pieces per group-0 wave (group 1 issues none)
   static_assert(PIECES % WN == 0, "DMA pieces must split over the waves");
+  static_assert(T::RPP == 1, "one 1-KB row per DMA piece");
   __shared__ __attribute__((aligned(1024))) char smem[2 * STAGE];
 
-  int kc, tile;
-  decode_kc_tile(blockIdx.x, p.nKc, p.nLt * p.nZt, kc, tile);
-  const int l0 = (tile / p.nZt) * BL, z0 = (tile % p.nZt) * BZ;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wid / WN, wn = wid % WN;
-  const int grp = wm;
-  const int lr = lane & 15, lg = lane >> 4;
-  const int rows = p.B * p.S;
-  const int q_begin = kc * p.rows_per_chunk;
-  const int q_end = min(p.rows_pad, q_begin + p.rows_per_chunk);
-  static_assert(RPP == 1, "one 1-KB row per DMA piece");
+  const DrCtx c = dr_ctx<T::BL, T::BZ, WN>(p.k, p.rows_pad);
+  const int grp = c.wm, wn = c.wn;
   // per-lane part of a piece's source offset: 16-B slot `lane` of the row
   // (32-B unit lane/2, swizzled by the row's r & 7, which cycles with the piece)
-  const int lane_u = lane >> 1, lane_h = (lane & 1) * 16;
-  const int tq = lr >> 2, tp = lr & 3;
-  const int r0 = lg * 4 + tq, r1 = r0 + 16, sw = r0 & 7;
+  const int lane_u = c.lane >> 1, lane_h = (c.lane & 1) * 16;
 
+  // (written out, in this order: the note in dR16_kernel)
   f32x4 acc[TM][TN];
 #pragma unroll
   for (int m = 0; m < TM; ++m)
 #pragma unroll
     for (int n = 0; n < TN; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  const int nst = (q_end - q_begin + kDrKR - 1) / kDrKR;
+  const int nst = (c.q_end - c.q_begin + kDrKR - 1) / kDrKR;
   if (grp == 0 && nst > 0) {
-    drs_issue_range<PIECES / WN, PIECES>(p, smem, q_begin, rows, wn * (PIECES / WN), l0, z0, lane_u,
-                                         lane_h);
+    drs_issue_range<PER_WAVE, PIECES>(p, smem, c.q_begin, c.rows, wn * PER_WAVE, c.l0, c.z0, lane_u,
+                                      lane_h);
     wait_vmcnt<0>();
   }
   DrFrag<TM, TN> f;
   DrsDma<PER_WAVE, PIECES, WN> dma;
-  if (grp == 0) dma.init(p, q_begin + kDrKR, wn, l0, z0);
+  if (grp == 0) dma.init(p, c.q_begin + kDrKR, wn, c.l0, c.z0);
   barrier_raw();
   // the two groups run the same number of barriers: 2*nst + 1
   if (grp == 0) {
@@ -997,21 +1020,20 @@ __global__ __launch_bounds__(WM* WN * 64, 1) void dR16s_kernel(Dr16Params p) {
     // of stage i, then stage i+1 landed before the closing barrier
     int i = 0;
     for (; i + 1 < nst; ++i) {
-      dr_read_dma<TM, TN, ROWB, IMG, PER_WAVE>(f, smem + (i & 1) * STAGE, wm, wn, r0, r1, sw, tp,
-                                               dma, smem + (1 - (i & 1)) * STAGE, rows, lane_u,
-                                               lane_h);
+      dr_read_dma<T, PER_WAVE>(f, smem + (i & 1) * STAGE, c, dma, smem + (1 - (i & 1)) * STAGE,
+                               lane_u, lane_h);
       lds_barrier();
       __builtin_amdgcn_s_setprio(1);
-      dr_mfma<TM, TN>(acc, f);
+      dr_mfma(acc, f);
       __builtin_amdgcn_s_setprio(0);
       wait_vmcnt<0>();
       barrier_raw();
     }
     for (; i < nst; ++i) {  // the last stage: nothing to stream
-      dr_read<TM, TN, ROWB, IMG>(f, smem + (i & 1) * STAGE, wm, wn, r0, r1, sw, tp);
+      dr_read<T>(f, smem + (i & 1) * STAGE, c);
       lds_barrier();
       __builtin_amdgcn_s_setprio(1);
-      dr_mfma<TM, TN>(acc, f);
+      dr_mfma(acc, f);
       __builtin_amdgcn_s_setprio(0);
       barrier_raw();
     }
@@ -1020,35 +1042,23 @@ __global__ __launch_bounds__(WM* WN * 64, 1) void dR16s_kernel(Dr16Params p) {
     barrier_raw();
     // slot 2i+1: read stage i; slot 2i+2: MFMAs of stage i
     for (int i = 0; i < nst; ++i) {
-      dr_read<TM, TN, ROWB, IMG>(f, smem + (i & 1) * STAGE, wm, wn, r0, r1, sw, tp);
+      dr_read<T>(f, smem + (i & 1) * STAGE, c);
       lds_barrier();
       __builtin_amdgcn_s_setprio(1);
-      dr_mfma<TM, TN>(acc, f);
+      dr_mfma(acc, f);
       __builtin_amdgcn_s_setprio(0);
       barrier_raw();
     }
   }
-  const float inv = 1.0f / (wave_pow2_scale(p.g_bound, p.B) * *p.eps16.scale);
-#pragma unroll
-  for (int m = 0; m < TM; ++m)
-#pragma unroll
-    for (int n = 0; n < TN; ++n)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int l = l0 + (wm * TM + m) * 16 + lg * 4 + i;
-        const int zc = z0 + (wn * TN + n) * 16 + lr;
-        if (l < p.L && zc < p.z) p.slab[((int64_t)kc * p.L + l) * p.z + zc] = acc[m][n][i] * inv;
-      }
+  dr_store_slab(acc, c, p.k, dr16_inv_scale(p));
 }
 
 // ---------------------------------------------------------------- dR GEMM
 struct DrParams {
   const float* G;    // (B*S, ldG): row q = b*S + s  (the T buffer)
   const float* eps;  // (S, B, z)
-  float* slab;       // [nKc][L][z]
-  int S, B, L, z;
+  DrCommon k;
   int ldG;  // t_cols(L)
-  int nLt, nZt, nKc, rows_per_chunk;
 };
 
 constexpr int kDrBK = 32;
@@ -1065,38 +1075,14 @@ __global__ __launch_bounds__(256) void dR_gemm_kernel(DrParams p) {
   float* Gs = smem;
   float* Es = smem + kDrBK * LDG;
 
-  // block -> (kc, tile); all tiles of one kc share eps/G rows: same id mod 8
-  const int nT = p.nLt * p.nZt;
-  int kc, tile;
-  {
-    const int id = blockIdx.x, K = p.nKc;
-    const int full = (K / 8) * 8 * nT;
-    if (id < full) {
-      const int q = id / (8 * nT), r = id % (8 * nT);
-      tile = r / 8;
-      kc = q * 8 + (r % 8);
-    } else {
-      const int r = id - full, Kr = K % 8;
-      tile = r / Kr;
-      kc = (K / 8) * 8 + (r % Kr);
-    }
-  }
-  const int l0 = (tile / p.nZt) * BM, z0 = (tile % p.nZt) * BN;
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int wm = wid / WN, wn = wid % WN;
-  const int lr = lane & 15, lg = lane >> 4;
-  const int S = p.S, B = p.B, L = p.L, z = p.z;
-  const int rows = B * S;
-  const int q_begin = kc * p.rows_per_chunk;
-  const int q_end = min(rows, q_begin + p.rows_per_chunk);
-  const bool gvec = true, evec = (z & 3) == 0;  // G rows: t_cols stride
+  const DrCtx ctx = dr_ctx<BM, BN, WN>(p.k, p.k.B * p.k.S);  // no pad rows: the tail loads zeros
+  const int l0 = ctx.l0, z0 = ctx.z0, wm = ctx.wm, wn = ctx.wn, lr = ctx.lr, lg = ctx.lg;
+  const int q_begin = ctx.q_begin, q_end = ctx.q_end;
+  const int tid = threadIdx.x;
+  const int S = p.k.S, B = p.k.B, L = p.k.L, z = p.k.z;
+  const bool evec = (z & 3) == 0;  // (G rows have the t_cols stride: whole float4s)
 
-  f32x4 acc[TM][TN];
-#pragma unroll
-  for (int m = 0; m < TM; ++m)
-#pragma unroll
-    for (int n = 0; n < TN; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
-
+  f32x4 acc[TM][TN] = {};
   f32x4 rg[GV], re[EV];
   auto load = [&](int q0) {
 #pragma unroll
@@ -1108,11 +1094,7 @@ __global__ __launch_bounds__(256) void dR_gemm_kernel(DrParams p) {
         const int q = q0 + r;
         if (q < q_end) {
           const float* src = p.G + (int64_t)q * p.ldG;
-          if (gvec && c < L) x = *reinterpret_cast<const f32x4*>(src + c);  // pads hold G = 0
-          else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) x[k] = (c + k < L) ? src[c + k] : 0.0f;
-          }
+          if (c < L) x = *reinterpret_cast<const f32x4*>(src + c);  // pads hold G = 0
         }
       }
       rg[v] = x;
@@ -1179,54 +1161,56 @@ __global__ __launch_bounds__(256) void dR_gemm_kernel(DrParams p) {
       }
     }
   }
-  // D[i = l][j = z]: row = lg*4 + reg, col = lr
-#pragma unroll
-  for (int m = 0; m < TM; ++m)
-#pragma unroll
-    for (int n = 0; n < TN; ++n)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int l = l0 + wm * TM * 16 + m * 16 + lg * 4 + i;
-        const int zc = z0 + wn * TN * 16 + n * 16 + lr;
-        if (l < L && zc < z) p.slab[((int64_t)kc * L + l) * z + zc] = acc[m][n][i];
-      }
+  dr_store_slab<false>(acc, ctx, p.k);
 }
 
 // ------------------------------------------------------------------- plans
+// A dR tile as the host sees it: its geometry, its split-K target and the
+// kernel that computes it.
+struct DrTile {
+  int edge;                      // output tile edge, labels and latent columns alike
+  int chunks_per_cu;             // split-K chunks per CU; 0: kDr32Blocks workgroups in all
+  int threads;
+  void (*kernel16)(Dr16Params);  // the 3xf16 kernel, or
+  void (*kernel32)(DrParams);    // the fp32 one
+};
+
+constexpr int kDr32Blocks = 1536;            // fp32 dR: workgroups aimed at (several per CU)
+constexpr int64_t kDrMaxChunkRows = 131072;  // longest split-K chunk (sample rows)
+
+static DrTile pick_dr_tile(int64_t L, int64_t z, int gemm) {
+  // fp32: 128 x 128, 4 waves of 64 x 64
+  if (gemm != MPV_GEMM_F16X3) return {128, 0, 256, nullptr, dR_gemm_kernel<4, 4>};
+  // Both <= 64 (mirflickr 38, the fairsoft adult-like 25 x 10): a 64 x 64 tile
+  // (4 waves of 32 x 32, 2 x 16 KB stages), planes padded to 64 columns: half
+  // the G-plane and noise-plane bytes of the 128 tile at L = z = 38.  Two K
+  // chunks per CU (4 and 8 measure the same at C2)
+  if (L <= 64 && z <= 64) return {64, 2, 256, dR16_kernel<2, 2, 2, 2>, nullptr};
+  // Both <= 128 (nuswide 81): a 128 x 128 tile (4 waves of 64 x 64, 2 x 32 KB
+  // stages, two workgroups per CU), so the G and noise planes are padded to
+  // 128 columns instead of 256
+  if (L <= 128 && z <= 128) return {128, 2, 256, dR16_kernel<2, 2, 4, 4>, nullptr};
+  // 256 x 256, 8 waves of 128 x 64 in two groups one phase apart, 2 x 64 KB
+  // stages: one workgroup per CU in a single wave of equal chunks
+  return {256, 1, 512, dR16s_kernel<2, 4, 8, 4>, nullptr};
+}
+
 struct BwdPlan {
-  int dr_tile;                                  // dR output tile edge
+  DrTile tile;
   int TPR, RPI, nLc, nSc, rows_per_chunk, Lc;   // element pass
   int nLt, nZt, nKc, dr_rows_per_chunk, rows_pad;  // dR GEMM
   int64_t ldg;                                  // G plane columns (3xf16, padded)
-  size_t coef_bytes, colpart_bytes, slab_bytes, bound_bytes, planes_bytes;
+  // the workspace: coef | colpart | slab | bound | G planes, each 256-B aligned
+  size_t coef_off, colpart_off, slab_off, bound_off, planes_off, end_off;
+  size_t total_bytes() const { return end_off; }
 };
-
-constexpr int kDr16Tile = 256;  // 3xf16 dR tile: 256 x 256, 8 waves of 128 x 64
-// Small label / latent dims (both <= 128, e.g. mirflickr 38, nuswide 81): a
-// 128 x 128 tile (4 waves of 64 x 64, two workgroups per CU), so the G and
-// noise planes are padded to 128 columns instead of 256
-constexpr int kDr16TileSmall = 128;
-
-// Both <= 64 (mirflickr 38, the fairsoft adult-like 25 x 10): a 64 x 64 tile
-// (4 waves of 32 x 32), planes padded to 64 columns: half the G-plane and
-// noise-plane bytes of the 128 tile at L = z = 38
-constexpr int kDr16TileTiny = 64;
-
-constexpr int kDrSmallChunksPerCu = 2;  // K chunks per CU for the 128 tile
-constexpr int kDrTinyChunksPerCu = 2;   // and for the 64 tile (4 and 8 measure the same at C2)
-constexpr int64_t kDrMaxChunkRows = 131072;  // longest split-K chunk (sample rows)
-
-static int dr16_tile(int64_t L, int64_t z) {
-  if (L <= kDr16TileTiny && z <= kDr16TileTiny) return kDr16TileTiny;
-  return (L <= kDr16TileSmall && z <= kDr16TileSmall) ? kDr16TileSmall : kDr16Tile;
-}
 
 static BwdPlan plan_bwd(const mpv_shape* s, int gemm) {
   BwdPlan pl;
   const int64_t L = s->L, S = s->S_local, B = s->B, z = s->z;
   const bool planes = gemm == MPV_GEMM_F16X3;
-  const int64_t dr_tile = planes ? dr16_tile(L, z) : 128;  // dR output tile edge
-  pl.dr_tile = (int)dr_tile;
+  pl.tile = pick_dr_tile(L, z, gemm);
+  const int64_t dr_tile = pl.tile.edge;
   pl.ldg = cdiv(L, dr_tile) * dr_tile;
   // columns the element pass covers: L rounded up to whole 4-column lane
   // groups (the pad columns get G = 0).  The G planes' columns beyond are
@@ -1261,12 +1245,9 @@ static BwdPlan plan_bwd(const mpv_shape* s, int gemm) {
   const int64_t tiles = (int64_t)pl.nLt * pl.nZt;
   const int64_t kr = 32;  // K rows per stage of either GEMM
   pl.rows_pad = (int)(cdiv(rows, kr) * kr);
-  // split-K chunks: the 3xf16 kernel (1 workgroup per CU) gets one workgroup
-  // per CU in a single wave of equal chunks; the fp32 kernel several per CU
-  const int cpc = dr_tile == kDr16Tile ? 1 : (dr_tile == kDr16TileTiny ? kDrTinyChunksPerCu
-                                                                      : kDrSmallChunksPerCu);
-  int64_t kc = planes ? cdiv(cpc * (int64_t)num_cus(), tiles)
-                      : cdiv(1536, tiles);
+  // split-K chunks: the workgroups the tile aims at (pick_dr_tile) over its tiles
+  const int cpc = pl.tile.chunks_per_cu;
+  int64_t kc = cdiv(cpc ? cpc * (int64_t)num_cus() : kDr32Blocks, tiles);
   // but no K chunk longer than kDrMaxChunkRows: one fp32 accumulator per output
   // over 4.2 M rows (C5 on one GPU: 256 tiles, so one chunk each) drifted 1e-4
   // (normwise) between two shardings of the same sum; chunks of <= 128 K rows
@@ -1277,11 +1258,19 @@ static BwdPlan plan_bwd(const mpv_shape* s, int gemm) {
   if (kc < 1) kc = 1;
   pl.dr_rows_per_chunk = (int)(cdiv(cdiv(rows, kc), kr) * kr);
   pl.nKc = (int)cdiv(rows, pl.dr_rows_per_chunk);
-  pl.coef_bytes = align_up(sizeof(float) * 6 * (size_t)B * S, 256);
-  pl.colpart_bytes = align_up(sizeof(float) * (size_t)pl.nSc * 2 * B * L, 256);
-  pl.slab_bytes = align_up(sizeof(float) * (size_t)pl.nKc * L * z, 256);
-  pl.bound_bytes = align_up(sizeof(float) * ((size_t)B + 64), 256);
-  pl.planes_bytes = planes ? align_up(2 * sizeof(uint16_t) * (size_t)pl.rows_pad * pl.ldg, 256) : 0;
+  size_t off = 0;
+  auto carve = [&off](size_t bytes) {
+    const size_t at = off;
+    off += align_up(bytes, 256);
+    return at;
+  };
+  pl.coef_off = carve(sizeof(float) * 6 * (size_t)B * S);
+  pl.colpart_off = carve(sizeof(float) * (size_t)pl.nSc * 2 * B * L);
+  pl.slab_off = carve(sizeof(float) * (size_t)pl.nKc * L * z);
+  pl.bound_off = carve(sizeof(float) * ((size_t)B + 64));
+  // chunked: rows_pad rows of 2 * ldg halves
+  pl.planes_off = carve(planes ? 2 * sizeof(uint16_t) * (size_t)pl.rows_pad * pl.ldg : 0);
+  pl.end_off = off;
   return pl;
 }
 
@@ -1293,14 +1282,13 @@ extern "C" {
 
 int64_t mpv_noise_plane_cols(const mpv_shape* shape) {
   if (check_shape(shape) != MPV_OK) return 0;
-  const int64_t t = dr16_tile(shape->L, shape->z);
+  const int64_t t = pick_dr_tile(shape->L, shape->z, MPV_GEMM_F16X3).edge;
   return cdiv(shape->z, t) * t;
 }
 
 size_t mpv_bwd_workspace_bytes(const mpv_shape* shape, int gemm) {
   if (check_shape(shape) != MPV_OK) return 0;
-  const BwdPlan pl = plan_bwd(shape, gemm);
-  return pl.coef_bytes + pl.colpart_bytes + pl.slab_bytes + pl.bound_bytes + pl.planes_bytes;
+  return plan_bwd(shape, gemm).total_bytes();
 }
 
 int mpv_probit_bwd(const mpv_shape* shape, const mpv_bwd_args* a, void* stream) {
@@ -1324,27 +1312,24 @@ int mpv_probit_bwd(const mpv_shape* shape, const mpv_bwd_args* a, void* stream) 
   if (dR_out) {
     if (planes) {
       MPV_REQUIRE(a->eps16.data && a->eps16.scale, "eps16 planes are NULL");
-      MPV_REQUIRE(a->eps16.ld >= 2 * (int64_t)pl.nZt * pl.dr_tile && a->eps16.ld % 64 == 0 &&
+      MPV_REQUIRE(a->eps16.ld >= 2 * (int64_t)pl.nZt * pl.tile.edge && a->eps16.ld % 64 == 0 &&
                       a->eps16.rows_pad >= shape->S_local * shape->B,
                   "eps16 planes too small (ld %lld < %lld: mpv_noise_plane_cols)",
-                  (long long)a->eps16.ld, 2 * (long long)pl.nZt * pl.dr_tile);
+                  (long long)a->eps16.ld, 2 * (long long)pl.nZt * pl.tile.edge);
     } else {
       MPV_REQUIRE(a->eps != nullptr, "MPV_GEMM_F32 needs eps");
     }
   }
-  const size_t need = pl.coef_bytes + pl.colpart_bytes + pl.slab_bytes + pl.bound_bytes +
-                      pl.planes_bytes;
-  MPV_REQUIRE(a->workspace_bytes >= need, "workspace too small: %zu < %zu", a->workspace_bytes,
-              need);
+  MPV_REQUIRE(a->workspace_bytes >= pl.total_bytes(), "workspace too small: %zu < %zu",
+              a->workspace_bytes, pl.total_bytes());
   hipStream_t st = as_stream(stream);
   char* ws = reinterpret_cast<char*>(a->workspace);
-  float* coef = reinterpret_cast<float*>(ws);
-  float* colpart = reinterpret_cast<float*>(ws + pl.coef_bytes);
-  float* slab = reinterpret_cast<float*>(ws + pl.coef_bytes + pl.colpart_bytes);
-  float* gbound = reinterpret_cast<float*>(ws + pl.coef_bytes + pl.colpart_bytes + pl.slab_bytes);
+  float* coef = reinterpret_cast<float*>(ws + pl.coef_off);
+  float* colpart = reinterpret_cast<float*>(ws + pl.colpart_off);
+  float* slab = reinterpret_cast<float*>(ws + pl.slab_off);
+  float* gbound = reinterpret_cast<float*>(ws + pl.bound_off);
   // G planes, chunked: rows_pad rows of gld = 2 * ldg halves
-  uint16_t* g16 = reinterpret_cast<uint16_t*>(ws + pl.coef_bytes + pl.colpart_bytes +
-                                              pl.slab_bytes + pl.bound_bytes);
+  uint16_t* g16 = reinterpret_cast<uint16_t*>(ws + pl.planes_off);
   const int64_t gld = 2 * pl.ldg;
   const int S = (int)shape->S_local, B = (int)shape->B, L = (int)shape->L, z = (int)shape->z;
   const bool want_planes = planes && dR_out != nullptr;
@@ -1369,27 +1354,10 @@ int mpv_probit_bwd(const mpv_shape* shape, const mpv_bwd_args* a, void* stream) 
     }
   }
 
-  ElemParams ep;
-  ep.y = a->y;
-  ep.fe = a->fe_out;
-  ep.fx = a->fx_out;
-  ep.gI = a->g_indiv;
-  ep.gIL = a->g_indiv_label;
-  ep.coef = coef;
-  ep.T = a->T;
-  ep.g = want_planes ? g16 : nullptr;
-  ep.g_bound = gbound;
-  ep.gld = gld;
-  ep.colpart = colpart;
-  ep.S = S;
-  ep.B = B;
-  ep.L = L;
-  ep.ldT = (int)t_cols(L);
-  ep.Lc = want_planes ? pl.Lc : L;
-  ep.TPR = pl.TPR;
-  ep.RPI = pl.RPI;
-  ep.rows_per_chunk = pl.rows_per_chunk;
-  ep.inv_S = 1.0f / (float)shape->S_total;
+  const ElemParams ep{a->y, a->fe_out, a->fx_out, a->g_indiv, a->g_indiv_label, coef, a->T,
+                      want_planes ? g16 : nullptr, gbound, gld, colpart, S, B, L,
+                      want_planes ? pl.Lc : L, (int)t_cols(L), pl.TPR, pl.RPI, pl.rows_per_chunk,
+                      1.0f / (float)shape->S_total};
   const dim3 eg(B, pl.nSc, pl.nLc);
   // t_cols rows: 16-B aligned, whole float4 reads
   if (want_planes && pl.RPI == 1)  // L >= 1024: the LDS-ring element pass
@@ -1405,47 +1373,14 @@ int mpv_probit_bwd(const mpv_shape* shape, const mpv_bwd_args* a, void* stream) 
   }
 
   if (dR_out) {
-    const int64_t blocks = (int64_t)pl.nLt * pl.nZt * pl.nKc;
+    const dim3 grid((unsigned)((int64_t)pl.nLt * pl.nZt * pl.nKc)), block(pl.tile.threads);
+    const DrCommon dc{slab, S, B, L, z, pl.nLt, pl.nZt, pl.nKc, pl.dr_rows_per_chunk};
     if (planes) {
-      Dr16Params dp;
-      dp.g = g16;
-      dp.g_bound = gbound;
-      dp.gld = gld;
-      dp.eps16 = a->eps16;
-      dp.slab = slab;
-      dp.S = S;
-      dp.B = B;
-      dp.L = L;
-      dp.z = z;
-      dp.nLt = pl.nLt;
-      dp.nZt = pl.nZt;
-      dp.nKc = pl.nKc;
-      dp.rows_per_chunk = pl.dr_rows_per_chunk;
-      dp.rows_pad = pl.rows_pad;
-      // 256 x 256 tile, 8 waves of 128 x 64, 2-stage ring (128 KB LDS)
-      static_assert(kDr16Tile == 256 && kDr16TileSmall == 128 && kDr16TileTiny == 64,
-                    "launch configs below");
-      if (pl.dr_tile == kDr16TileTiny)  // 64 x 64, 4 waves of 32 x 32, 2 x 16 KB stages
-        MPV_LAUNCH("dR_gemm", (dR16_kernel<2, 2, 2, 2, 2>), dim3((unsigned)blocks), dim3(256), 0, st, dp);
-      else if (pl.dr_tile == kDr16TileSmall)  // 128 x 128, 4 waves of 64 x 64, 2 x 32 KB stages
-        MPV_LAUNCH("dR_gemm", (dR16_kernel<2, 2, 4, 4, 2>), dim3((unsigned)blocks), dim3(256), 0, st, dp);
-      else  // 256 x 256, two wave groups one phase apart (dR16s)
-        MPV_LAUNCH("dR_gemm", (dR16s_kernel<2, 4, 8, 4>), dim3((unsigned)blocks), dim3(512), 0, st, dp);
+      const Dr16Params dp{g16, gbound, gld, a->eps16, dc, pl.rows_pad};
+      MPV_LAUNCH("dR_gemm", pl.tile.kernel16, grid, block, 0, st, dp);
     } else {
-      DrParams dp;
-      dp.G = a->T;
-      dp.eps = a->eps;
-      dp.slab = slab;
-      dp.S = S;
-      dp.B = B;
-      dp.L = L;
-      dp.ldG = (int)t_cols(L);
-      dp.z = z;
-      dp.nLt = pl.nLt;
-      dp.nZt = pl.nZt;
-      dp.nKc = pl.nKc;
-      dp.rows_per_chunk = pl.dr_rows_per_chunk;
-      MPV_LAUNCH("dR_gemm", (dR_gemm_kernel<4, 4>), dim3((unsigned)blocks), dim3(256), 0, st, dp);
+      const DrParams dp{a->T, a->eps, dc, (int)t_cols(L)};
+      MPV_LAUNCH("dR_gemm", pl.tile.kernel32, grid, block, 0, st, dp);
     }
     if (int rc = check_launch("dR_gemm")) return rc;
     // the column partials (d fe_out, d fx_out) and the dR slabs in one launch

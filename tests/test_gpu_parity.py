@@ -289,6 +289,7 @@ RANDOM_CASES = [
     (2, 100, 4, 33, 8),          # two labels
     (129, 128, 2, 50, 8),        # one label past the small tile: 256 tile
     (200, 64, 5, 257, 8),        # two column tiles, ragged s tiles
+    (200, 64, 4, 600, 8),        # 256 dR tile, 10 split-K chunks: 8 + a remainder of 2, short last
     (1024, 1024, 2, 48, 50),     # C4 dims, tiny batch
     (1030, 96, 2, 20, 8),        # L > 1024: two bwd column chunks
     (700, 64, 3, 130, 8),        # 512 < L < 1024: ring element pass with masked waves
