@@ -194,7 +194,11 @@ def test_graph_captured_step_draws_fresh_noise_per_replay():
 
 @pytest.mark.parametrize("key_on_device", [True, False])
 @pytest.mark.parametrize("L,z,rdt", [(38, 38, torch.float64), (81, 81, torch.float32),
-                                     (128, 128, torch.float64), (3, 2, torch.float64)])
+                                     (128, 128, torch.float64), (3, 2, torch.float64),
+                                     # non-narrow noise: the split's workgroups have the
+                                     # noise launch's 64 / 128 / 192 / 256 (column-stride) threads
+                                     (32, 512, torch.float64), (16, 1024, torch.float32),
+                                     (10, 1536, torch.float64), (4, 2048, torch.float32)])
 def test_noise_with_r_split_is_the_two_launches(L, z, rdt, key_on_device):
     """mpv_noise_philox_f16_split (the r_sqrt_sigma split riding on the noise
     launch, L * z <= 16384) writes exactly what mpv_noise_philox_f16(_dev) and

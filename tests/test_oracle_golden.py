@@ -77,6 +77,82 @@ def test_philox_noise_is_standard_normal_and_shard_invariant():
     np.testing.assert_array_equal(a, n[24:64])
 
 
+def test_philox_u_is_the_device_fp32_map():
+    """Box-Muller's u is formed as the device forms it, fp32(m + 0.5) * 2^-24:
+    the fp64 (m + 0.5) 2^-24 for every m < 2^23, exactly 2^-25 off it (round to
+    even) from there on.  The radius moves by at most 2^-25 / (u r) -- the
+    mean-value bound with u r = u sqrt(-2 ln u) at the smaller of the two ends,
+    where it is smallest on the interval (u r rises up to u = e^-1/2, then
+    falls) -- except at m = 2^24 - 1, where the device's u is 1 and r = 0."""
+    m = np.arange(1 << 24, dtype=np.uint32)
+    u = philox.uniform_u(m)
+    assert u.dtype == np.float64
+    u64 = (m.astype(np.float64) + 0.5) * 2.0 ** -24
+    lo = m < (1 << 23)
+    assert np.array_equal(u[lo], u64[lo])
+    d = u[~lo] - u64[~lo]
+    assert np.array_equal(np.abs(d), np.full(d.shape, 2.0 ** -25))
+    # round to even: up for odd m, down for even m
+    assert np.array_equal(d > 0, (m[~lo] & 1) == 1)
+    assert u.min() == 2.0 ** -25 and u.max() == 1.0 and (u > 0).all()
+    r, r64 = np.sqrt(-2.0 * np.log(u[~lo])), np.sqrt(-2.0 * np.log(u64[~lo]))
+    dr = np.abs(r - r64)
+    assert r[-1] == 0.0 and abs(r64[-1] - 2.0 ** -12) < 1e-10   # sqrt(2 * 2^-25)
+    ur = np.minimum(u[~lo] * r, u64[~lo] * r64)[:-1]
+    # (2^-50: the fp64 rounding of the two radii, four ulps of r <= 1.18)
+    assert (dr[:-1] <= 2.0 ** -25 / ur + 2.0 ** -50).all()
+    # what the old fp64 map cost against the device: 19 values of m beyond
+    # 2e-5 (the GPU noise test's bound): 6.5e-5 at m = 2^24 - 2, 2.4e-4 at the top
+    assert int((dr > 2e-5).sum()) == 19 and dr[:-1].max() < 7e-5 and dr.argmax() == len(dr) - 1
+
+
+def test_philox_normal_noise_is_normal_at_of_its_indices():
+    S, B, z, seed = 5, 3, 13, 0x1234ABCD5678
+    for s_off, off in ((0, 0), (7, 5), (2 ** 34 // 39 - 2, 0), (2 ** 40 + 3, 2 ** 63), (0, 2 ** 64 - 2)):
+        e0 = s_off * B * z
+        e = np.array([e0 + i for i in range(S * B * z)], np.uint64)
+        n = philox.normal_noise(S, B, z, seed, offset=off, s_offset=s_off)
+        assert n.shape == (S, B, z) and n.dtype == np.float64
+        np.testing.assert_array_equal(n.ravel(), philox.normal_at(e, seed, off))
+        # any order, any shape; one element at a time
+        p = np.random.default_rng(1).permutation(len(e))[:24].reshape(2, 3, 4)
+        np.testing.assert_array_equal(philox.normal_at(e[p], seed, off), n.ravel()[p])
+    # the counter is (e div 4 + offset) mod 2^64, as (lo, hi, 0, 0)
+    w = philox.philox4x32_10(1, 0, 0, 0, seed & 0xFFFFFFFF, seed >> 32)
+    want = philox.box_muller(w[2], w[3])[1]
+    got = philox.normal_at(np.array([7 + 4 * 3], np.uint64), seed, offset=2 ** 64 - 3)  # ctr 4 - 3
+    assert float(got[0]) == float(want)
+    w = philox.philox4x32_10(0xFFFFFFFF, 0x12, 0, 0, seed & 0xFFFFFFFF, seed >> 32)
+    got = philox.normal_at(np.array([4 * 0xFFFFFFFF], np.uint64), seed, offset=0x12 << 32)
+    assert float(got[0]) == float(philox.box_muller(w[0], w[1])[0])
+
+
+def test_philox_edge_fixture_regenerates_to_the_committed_bytes(golden_dir):
+    """tests/golden/philox_edges.npz is what its generator writes (a scan of
+    2^23 counters by the oracle), and holds the edges it is there for."""
+    import importlib.util
+    import os
+    spec = importlib.util.spec_from_file_location(
+        "_make_golden_philox_edges", os.path.join(golden_dir, "make_golden_philox_edges.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    t = gen.tables()
+    with open(os.path.join(golden_dir, "philox_edges.npz"), "rb") as f:
+        committed = f.read()
+    assert gen.npz_bytes(t) == committed
+    assert len(committed) < 16384
+    cls, me, mo = t["cls"], t["m_even"].astype(np.int64), t["m_odd"].astype(np.int64)
+    for k, name in enumerate(gen.CLASSES):
+        assert 0 < (cls == k).sum() <= 32, name
+    assert (me[cls == 0] < 256).all() and (me[cls == 0] == 0).any()
+    assert (me[cls == 1] >= 2 ** 24 - 256).all() and (me[cls == 1] == 2 ** 24 - 1).any()
+    for k, q in ((2, 0), (3, 2 ** 22), (4, 2 ** 23), (5, 3 * 2 ** 22)):
+        d = (mo[cls == k] - q) % 2 ** 24
+        assert (np.minimum(d, 2 ** 24 - d) <= 256).all()
+    w = np.stack(philox.words_at(t["counter"], int(t["key"][0])), -1)
+    assert np.array_equal(w, t["words"])
+
+
 @pytest.mark.parametrize("f", [f for f in FIX if f.mode == "train"][:4],
                          ids=[f.name for f in FIX if f.mode == "train"][:4])
 def test_torch_restatement_matches_reference(f):

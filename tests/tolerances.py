@@ -105,6 +105,18 @@ METRIC_COUNT_ULP = 2.0 ** -52          # times B
 # Measured <= 4.2e-8 absolute.
 METRIC_F1_RTOL, METRIC_F1_ATOL = 1e-6, 1e-7
 
+# Device Philox noise (csrc/util.hip: the fp32 draw and the 3xf16 planes, one
+# bound for both) against oracle/philox.py, absolute (tests/test_gpu_noise.py:
+# every launch geometry, counters beyond 32 bits, call offsets, the Box-Muller
+# edges of tests/golden/philox_edges.npz, the fp32 grid-stride loop).  The
+# oracle forms Box-Muller's u in fp32 exactly as the device does, so what is
+# left is the hardware log2 / sqrt / sin / cos in fp32 and, for the planes, the
+# split's 2^-22 |n| <= 1.4e-6.  Measured on the MI355X over the 38 cases
+# (profiles/noise_errs.jsonl): fp32 draw <= 5.4e-7, planes <= 9.4e-7 (the
+# largest among the edge counters with u -> 2^-25, |n| from 4.7 to 5.9).
+# About 2x that; the older test_philox_noise_matches_oracle keeps its 2e-5.
+NOISE_ATOL = 2e-6
+
 
 def fair_row_grad_tol(s):
     """Bound of the per-row gradient check of the fairness penalty,
