@@ -23,10 +23,13 @@
 //                    groups one phase apart, the 256 tile.
 //   dR_gemm_kernel   the same on exact fp32 MFMA (MPV_GEMM_F32), 128 tile.
 //                    Shared by the three: Dr16Tile (geometry), dr_ctx (what a
-//                    workgroup and its lanes own), dr_read + dr_mfma on a DrFrag
-//                    (3xf16), dr_store_slab.
+//                    workgroup and its lanes own), dr_mfma on a DrFrag (3xf16)
+//                    filled by dr_read (dR16_kernel) or, from constant per-lane
+//                    bases, by drs_read (dR16s_kernel: DrsAddr), dr_store_slab.
 // Host: pick_dr_tile chooses the DrTile descriptor (edge, split-K target,
 // threads, kernel); plan_bwd derives the grids and the workspace layout from it.
+#include <type_traits>
+
 #include "abi_util.h"
 #include "mpv_common.h"
 
@@ -622,7 +625,8 @@ struct DrCommon {
 // for both operands.  The rows stream in stages of 32 through a ring of LDS
 // stage images (LDS-DMA, one barrier per stage).  Both operands are chunked
 // (mpv_split16), so the 128 columns of a tile are 512 contiguous bytes per row
-// holding hi and lo; a stage image is [G rows | E rows], 32 rows x 512 B each,
+// holding hi and lo; a stage image is [G rows | E rows], 32 rows x 512 B each
+// (the 256 tile keeps the operands' images apart: DrsAddr),
 // and one DMA wave-instruction moves two whole rows.  The 32-B unit U of row r
 // (units 4k, 4k+1: hi of columns 32k..32k+31; 4k+2, 4k+3: their lo) sits at
 // position U ^ (r & 7).  An MFMA fragment (8 K rows of one column per lane) is
@@ -857,71 +861,95 @@ __global__ __launch_bounds__(WM* WN * 64, 1) void dR16_kernel(Dr16Params p) {
       dr_issue<PER_WAVE, PIECES, RPP>(p, smem + ((ci + 1) % 2) * STAGE,
                                       c.q_begin + (ci + 1) * kDrKR, c.rows, c.wid, dma_off);
     DrFrag<TM, TN> f;
-    // (an LDS-typed base: through the generic pointer dR16s_kernel still passes,
-    // hipcc here adds the lane's row offset again at every read, 15 more VALU
-    // instructions per stage of the 128 tile)
+    // (an LDS-typed base: through a generic pointer hipcc adds the lane's row
+    // offset again at every read, 15 more VALU instructions per stage of the
+    // 128 tile)
     dr_read<T>(f, (lds_cptr)(smem + (ci % 2) * STAGE), c);
     dr_mfma(acc, f);
   }
   dr_store_slab(acc, c, p.k, dr16_inv_scale(p));
 }
 
-// dr_read with a group-0 wave's share of the next stage's LDS-DMA woven in:
-// one or two 1-KB pieces after each tile's four transposed reads, so the
-// CU's load path (the DMA) and the LDS (the reads) work side by side instead
-// of the reads queueing behind the whole DMA burst (profiles/r05_dr_ab.json: DMA
-// issue 1060 + reads 960 ticks, serial, against 1650 for the other group's
-// MFMAs).  Noise rows past the last real one (a padded last stage) repeat
-// that row, as drs_issue_range clamps them.
-template <class T, int PER_WAVE, class Dma>
-MPV_DEV void dr_read_dma(DrFrag<T::TM, T::TN>& f, const char* base, const DrCtx& c, Dma& dma,
-                         char* dst, int lane_u, int lane_h) {
-  constexpr int TM = T::TM, TN = T::TN, ROWB = T::ROWB, IMG = T::IMG, STEPS = TM + TN;
-  const int wm = c.wm, wn = c.wn, r0 = c.r0, r1 = c.r1, sw = c.sw, tp = c.tp, rows = c.rows;
-  // the per-piece source swizzle is recomputed next to its DMA, not hoisted
-  // out of the stage loop (8 more live VGPRs spill the accumulators)
-  int lu = lane_u;
-  asm volatile("" : "+v"(lu));
-  const char* sp = dma.src;
-  int nvalid = PER_WAVE;
-  if (!dma.is_g) {
-    const int over = dma.q - (rows - 1);
-    if (over > 0) sp -= over * dma.row_b;
-    nvalid = max(1, min(PER_WAVE, rows - dma.q));
-  }
+// ---- the 256 tile's ring, fragment addresses and stage DMA (dR16s_kernel) ----
+// Its ring holds the two stage images operand by operand,
+//   [G stage 0 | G stage 1 | E stage 0 | E stage 1],  IMG bytes each,
+// so both parities of an operand lie within 64 KB of one base and a transposed
+// read's whole stage / row / unit-group displacement fits ds_read's 16-bit
+// offset field.  A lane reads  r*ROWB + ((uh ^ sw) << 5) + tp*8  of an image,
+// uh = (t>>1)*4 + (t&1) (+2 for a lo unit) and t = w*TT + i the wave's i-th
+// tile; with TT a multiple of 4, uh = w*2*TT + uhi and only uhi & 7 meets the
+// 3-bit sw.  So eight bases per operand, one per value of (uhi & 7) ^ sw with
+// r0*ROWB, tp*8 and the wave's w*TT*64 folded in, and everything else is an
+// immediate: (uhi >> 3)*256, row r1 = r0 + 16 at +16*ROWB, stage parity at
+// +IMG.  16 address VGPRs, fixed for the kernel's life; no address arithmetic
+// in the stage loops (the [G|E][G|E] ring with a run-time stage base took
+// 48-79 VALU per stage to rebuild these addresses from the parity).
+template <class T>
+struct DrsAddr {
+  static_assert(T::TM % 4 == 0 && T::TN % 4 == 0, "a wave's units start at a multiple of 8");
+  static_assert(T::IMG + 16 * T::ROWB + ((2 * (T::TM > T::TN ? T::TM : T::TN) - 1) >> 3) * 256 < 65536,
+                "the displacements fit ds_read's offset field");
+  lds_cptr a[8], b[8];
+  MPV_DEV void init(lds_cptr ring, const DrCtx& c) {
+    const int lane_b = c.r0 * T::ROWB + c.tp * 8;
 #pragma unroll
-  for (int k = 0; k < STEPS; ++k) {
-    const bool is_a = k < TM;
-    const int t = is_a ? wm * TM + k : wn * TN + (k - TM), uh = (t >> 1) * 4 + (t & 1);
-    const int ch = ((uh ^ sw) << 5) + tp * 8, cl = (((uh + 2) ^ sw) << 5) + tp * 8;
-    const char* img = is_a ? base : base + IMG;
-    const s16x8 hi = __builtin_shufflevector(tr_read(img, r0 * ROWB + ch), tr_read(img, r1 * ROWB + ch),
-                                             0, 1, 2, 3, 4, 5, 6, 7);
-    const s16x8 lo = __builtin_shufflevector(tr_read(img, r0 * ROWB + cl), tr_read(img, r1 * ROWB + cl),
-                                             0, 1, 2, 3, 4, 5, 6, 7);
-    if (is_a) {
-      f.ah[k] = hi;
-      f.al[k] = lo;
-    } else {
-      f.bh[k - TM] = hi;
-      f.bl[k - TM] = lo;
+    for (int j = 0; j < 8; ++j) {
+      a[j] = ring + (c.wm * T::TM * 64 + lane_b + ((j ^ c.sw) << 5));
+      b[j] = ring + (2 * T::IMG + c.wn * T::TN * 64 + lane_b + ((j ^ c.sw) << 5));
+      // opaque from here on: hipcc otherwise keeps sw and rebuilds them per stage
+      asm volatile("" : "+v"(a[j]));
+      asm volatile("" : "+v"(b[j]));
     }
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int i = k * PER_WAVE / STEPS; i < (k + 1) * PER_WAVE / STEPS; ++i) {
-      lds_dma16(sp, (uint32_t)(((lu ^ (i & 7)) << 5) + lane_h), lds_addr(dst + (dma.pc0 + i) * 1024));
-      sp += (i + 1 < nvalid) ? dma.row_b : 0;
-    }
-    __builtin_amdgcn_sched_barrier(0);
   }
-  dma.end();
+};
+
+// hi (LO = 0) or lo (LO = 2) fragment of the wave's I-th tile, stage parity PAR
+template <class T, int PAR, int I, int LO>
+MPV_DEV s16x8 drs_frag(const lds_cptr (&base)[8]) {
+  constexpr int uhi = (I >> 1) * 4 + (I & 1) + LO;
+  constexpr int off = PAR * T::IMG + (uhi >> 3) * 256;
+  return __builtin_shufflevector(tr_read(base[uhi & 7], off),
+                                 tr_read(base[uhi & 7], off + 16 * T::ROWB), 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
+// Step K of a stage's reads: the hi and lo fragments of one tile, A tiles first
+// (the order of dr_read).
+template <class T, int PAR, int K>
+MPV_DEV void drs_read_step(DrFrag<T::TM, T::TN>& f, const DrsAddr<T>& ad) {
+  if constexpr (K < T::TM) {
+    f.ah[K] = drs_frag<T, PAR, K, 0>(ad.a);
+    f.al[K] = drs_frag<T, PAR, K, 2>(ad.a);
+  } else {
+    f.bh[K - T::TM] = drs_frag<T, PAR, K - T::TM, 0>(ad.b);
+    f.bl[K - T::TM] = drs_frag<T, PAR, K - T::TM, 2>(ad.b);
+  }
+}
+
+template <class T, int PAR, int K = 0>
+MPV_DEV void drs_read(DrFrag<T::TM, T::TN>& f, const DrsAddr<T>& ad) {
+  if constexpr (K < T::TM + T::TN) {
+    drs_read_step<T, PAR, K>(f, ad);
+    drs_read<T, PAR, K + 1>(f, ad);
+  }
+}
+
+// lds_dma16 to LDS byte lds_base + OFF, with M0 set by one scalar add and left
+// there: nothing else in dR16s_kernel reads or sets M0 (gfx950's ds_read needs
+// none; checked in its assembly).  M0 is reserved to hipcc, which sets it right
+// at each use of its own, so it cannot be named as a clobber.
+template <int OFF>
+MPV_DEV void lds_dma16_at(const void* saddr, uint32_t voff, uint32_t lds_base) {
+  asm volatile("s_add_u32 m0, %2, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
+               :
+               : "v"(voff), "s"(saddr), "s"(lds_base), "n"(OFF)
+               : "memory", "scc");
 }
 
 // Pieces pc0 .. pc0+COUNT-1 of one stage's LDS-DMA (one row each: the first
-// PIECES/2 are G rows, the rest E rows).
+// PIECES/2 are G rows into dst_g, the rest E rows into dst_e).
 template <int COUNT, int PIECES>
-MPV_DEV void drs_issue_range(const Dr16Params& p, char* dst, int q0, int rows, int pc0, int l0,
-                             int z0, int lane_u, int lane_h) {
+MPV_DEV void drs_issue_range(const Dr16Params& p, char* dst_g, char* dst_e, int q0, int rows,
+                             int pc0, int l0, int z0, int lane_u, int lane_h) {
 #pragma unroll
   for (int i = 0; i < COUNT; ++i) {
     const int pc = pc0 + i;  // wave-uniform
@@ -932,7 +960,8 @@ MPV_DEV void drs_issue_range(const Dr16Params& p, char* dst, int q0, int rows, i
                            : reinterpret_cast<const char*>(p.eps16.data +
                                                            (int64_t)min(q, rows - 1) * p.eps16.ld +
                                                            2 * z0);
-    lds_dma16(src, (uint32_t)(((lane_u ^ (r & 7)) << 5) + lane_h), lds_addr(dst + pc * 1024));
+    lds_dma16(src, (uint32_t)(((lane_u ^ (r & 7)) << 5) + lane_h),
+              lds_addr((is_g ? dst_g : dst_e) + r * 1024));
   }
 }
 
@@ -943,27 +972,74 @@ MPV_DEV void drs_issue_range(const Dr16Params& p, char* dst, int q0, int rows, i
 // 139 instructions, dR -1.5 %, profiles/r05_dr_dma_ab.json).
 template <int PER_WAVE, int PIECES, int WN>
 struct DrsDma {
-  const char* src;  // first row of this wave's share of the next stage
-  int64_t row_b;    // bytes per source row
-  int q;            // its row index
-  int pc0;          // first piece (1-KB LDS row) of the share
+  const char* src;    // first row of this wave's share of the next stage
+  int64_t row_b;      // bytes per source row
+  int r_first;        // that row's place in the stage
+  uint32_t lds_base;  // LDS byte address of the share in its operand's stage-0 image
   bool is_g;
-  MPV_DEV void init(const Dr16Params& p, int q_first, int wn, int l0, int z0) {
+  MPV_DEV void init(const Dr16Params& p, int q_begin, int wn, int l0, int z0, uint32_t ring,
+                    int img) {
     static_assert(PIECES / 2 == (WN / 2) * PER_WAVE, "G rows on the first half of the waves");
     static_assert(PER_WAVE % 8 == 0, "the source swizzle (row & 7) restarts with every share");
     const int pc = wn * PER_WAVE;
     is_g = pc < PIECES / 2;
-    pc0 = pc;
-    q = q_first + (is_g ? pc : pc - PIECES / 2);
+    r_first = is_g ? pc : pc - PIECES / 2;
+    lds_base = ring + (is_g ? 0 : 2 * img) + r_first * 1024;
+    const int q = q_begin + kDrKR + r_first;  // the first stage it streams is stage 1
     row_b = is_g ? p.gld * 2 : p.eps16.ld * 2;
     src = is_g ? reinterpret_cast<const char*>(p.g + (int64_t)q * p.gld + 2 * l0)
                : reinterpret_cast<const char*>(p.eps16.data + (int64_t)q * p.eps16.ld + 2 * z0);
   }
-  MPV_DEV void end() {  // on to the next stage
-    src += kDrKR * row_b;
-    q += kDrKR;
-  }
 };
+
+// drs_read of stage parity PAR with a group-0 wave's share of the next stage's
+// LDS-DMA (into the images of parity 1 - PAR) woven in: one or two 1-KB pieces
+// after each tile's four transposed reads, so the CU's load path (the DMA) and
+// the LDS (the reads) work side by side instead of the reads queueing behind
+// the whole DMA burst (profiles/r05_dr_ab.json: DMA issue 1060 + reads 960
+// ticks, serial, against 1650 for the other group's MFMAs).  A piece is a
+// pointer step (2 SALU), the M0 add, a wait state and the DMA, its lanes'
+// source swizzle voff ^ (row & 7) << 5 being loop-invariant.  TAIL: the stage streamed is the chunk's last and may be the padded
+// one (q_next = its first row of this share): noise rows past the last real
+// one repeat that row, as drs_issue_range clamps them; G rows there are zero
+// in the planes (rows_pad).  Only that stage pays the compare and selects.
+// pieces I .. END-1 of the share
+template <class T, int PAR, bool TAIL, int I, int END, class Dma>
+MPV_DEV void drs_pieces(const Dma& dma, const char*& sp, int nvalid, uint32_t voff) {
+  if constexpr (I < END) {
+    lds_dma16_at<(1 - PAR) * T::IMG + I * 1024>(sp, voff ^ ((I & 7) << 5), dma.lds_base);
+    if constexpr (TAIL) sp += (I + 1 < nvalid) ? dma.row_b : 0;
+    else sp += dma.row_b;
+    drs_pieces<T, PAR, TAIL, I + 1, END>(dma, sp, nvalid, voff);
+  }
+}
+
+template <class T, int PER_WAVE, int PAR, bool TAIL, int K = 0, class Dma>
+MPV_DEV void drs_read_dma_steps(DrFrag<T::TM, T::TN>& f, const DrsAddr<T>& ad, const Dma& dma,
+                                const char*& sp, int nvalid, uint32_t voff) {
+  constexpr int STEPS = T::TM + T::TN;
+  if constexpr (K < STEPS) {
+    drs_read_step<T, PAR, K>(f, ad);
+    __builtin_amdgcn_sched_barrier(0);
+    drs_pieces<T, PAR, TAIL, K * PER_WAVE / STEPS, (K + 1) * PER_WAVE / STEPS>(dma, sp, nvalid, voff);
+    __builtin_amdgcn_sched_barrier(0);
+    drs_read_dma_steps<T, PER_WAVE, PAR, TAIL, K + 1>(f, ad, dma, sp, nvalid, voff);
+  }
+}
+
+template <class T, int PER_WAVE, int PAR, bool TAIL, class Dma>
+MPV_DEV void drs_read_dma(DrFrag<T::TM, T::TN>& f, const DrsAddr<T>& ad, Dma& dma, int q_next,
+                          int rows, uint32_t voff) {
+  const char* sp = dma.src;
+  int nvalid = PER_WAVE;
+  if (TAIL && !dma.is_g) {
+    const int over = q_next - (rows - 1);
+    if (over > 0) sp -= over * dma.row_b;
+    nvalid = max(1, min(PER_WAVE, rows - q_next));
+  }
+  drs_read_dma_steps<T, PER_WAVE, PAR, TAIL>(f, ad, dma, sp, nvalid, voff);
+  dma.src += kDrKR * dma.row_b;  // on to the next stage
+}
 
 // Staggered schedule: the waves of row wm = 0 (group 0) and wm = 1 (group 1)
 // share the SIMDs pairwise and run one phase apart, so on every SIMD one wave
@@ -971,11 +1047,12 @@ struct DrsDma {
 // one barrier each; group 0 does mem(i) in slot 2i and mma(i) in slot 2i+1,
 // group 1 does mem(i) in slot 2i+1 and mma(i) in slot 2i+2.
 //   mem(i): fragment reads of stage i; group 0 weaves the LDS-DMA of stage i+1
-//           into image (i+1)%2 (read by group 1 in slot 2i-1, so free) into
-//           them (dr_read_dma).
+//           into the other parity's images (read by group 1 in slot 2i-1, so
+//           free) into them (drs_read_dma).
 //   mma(i): 96 MFMAs; group 0 then waits for its stage i+1 DMA, so stage i+1
 //           is visible to both groups after the slot's barrier.
-// Two 64-KB stage images; DMA latency budget = one slot pair.  Round 5
+// Two 64-KB stage images (laid out operand by operand: DrsAddr); DMA latency
+// budget = one slot pair.  Round 5
 // (the slot-timing study in profiles/r05_dr_ab.json): with the DMA as a burst ahead
 // of the reads, group 0's mem slot (1060 + 960 ticks) outlasted the other
 // group's MFMAs (1650) every slot; woven, dR -4.2 %.  Measured slower: group 1
@@ -986,11 +1063,12 @@ template <int WM, int WN, int TM, int TN>
 __global__ __launch_bounds__(WM* WN * 64, 1) void dR16s_kernel(Dr16Params p) {
   static_assert(WM == 2, "two wave groups");
   using T = Dr16Tile<WM, WN, TM, TN>;
-  constexpr int STAGE = T::STAGE, PIECES = T::PIECES;
+  constexpr int IMG = T::IMG, PIECES = T::PIECES;
   constexpr int PER_WAVE = PIECES / WN;  // pieces per group-0 wave (group 1 issues none)
   static_assert(PIECES % WN == 0, "DMA pieces must split over the waves");
   static_assert(T::RPP == 1, "one 1-KB row per DMA piece");
-  __shared__ __attribute__((aligned(1024))) char smem[2 * STAGE];
+  // [G stage 0 | G stage 1 | E stage 0 | E stage 1] (DrsAddr)
+  __shared__ __attribute__((aligned(1024))) char smem[4 * IMG];
 
   const DrCtx c = dr_ctx<T::BL, T::BZ, WN>(p.k, p.rows_pad);
   const int grp = c.wm, wn = c.wn;
@@ -1005,48 +1083,75 @@ __global__ __launch_bounds__(WM* WN * 64, 1) void dR16s_kernel(Dr16Params p) {
 #pragma unroll
     for (int n = 0; n < TN; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
   const int nst = (c.q_end - c.q_begin + kDrKR - 1) / kDrKR;
+  // Stage i lives in the images of parity (i + p0) & 1, p0 = nst & 1: the last
+  // stage always has parity 1 and the one before it parity 0, so the peeled
+  // end of the chunk is one code path and the odd stage is peeled at the front.
+  const int p0 = nst & 1;
   if (grp == 0 && nst > 0) {
-    drs_issue_range<PER_WAVE, PIECES>(p, smem, c.q_begin, c.rows, wn * PER_WAVE, c.l0, c.z0, lane_u,
-                                      lane_h);
+    drs_issue_range<PER_WAVE, PIECES>(p, smem + p0 * IMG, smem + (2 + p0) * IMG, c.q_begin, c.rows,
+                                      wn * PER_WAVE, c.l0, c.z0, lane_u, lane_h);
     wait_vmcnt<0>();
   }
   DrFrag<TM, TN> f;
-  DrsDma<PER_WAVE, PIECES, WN> dma;
-  if (grp == 0) dma.init(p, c.q_begin + kDrKR, wn, c.l0, c.z0);
+  DrsAddr<T> ad;
+  ad.init((lds_cptr)smem, c);
   barrier_raw();
-  // the two groups run the same number of barriers: 2*nst + 1
+  // the second slot of a stage: its 96 MFMAs
+  auto mma = [&]() {
+    lds_barrier();
+    __builtin_amdgcn_s_setprio(1);
+    dr_mfma(acc, f);
+    __builtin_amdgcn_s_setprio(0);
+  };
+  // The stage loops are unrolled by parity, so every LDS displacement is an
+  // immediate; a chunk with an odd number of stages skips the first pair's
+  // parity-0 half.  The two groups run the same number of barriers: 2*nst + 1
+  bool skip = p0;
   if (grp == 0) {
+    DrsDma<PER_WAVE, PIECES, WN> dma;
+    dma.init(p, c.q_begin, wn, c.l0, c.z0, lds_addr(smem), IMG);
+    // (a piece's swizzle is written as an xor next to its DMA; hipcc hoists the
+    // eight values out of the loops on its own, registers permitting: forced
+    // into registers beside the 16 read bases they spilled the accumulators)
+    const uint32_t voff = (uint32_t)((lane_u << 5) + lane_h);
     // slot 2i: read stage i with stage i+1's DMA woven in; slot 2i+1: MFMAs
     // of stage i, then stage i+1 landed before the closing barrier
-    int i = 0;
-    for (; i + 1 < nst; ++i) {
-      dr_read_dma<T, PER_WAVE>(f, smem + (i & 1) * STAGE, c, dma, smem + (1 - (i & 1)) * STAGE,
-                               lane_u, lane_h);
-      lds_barrier();
-      __builtin_amdgcn_s_setprio(1);
-      dr_mfma(acc, f);
-      __builtin_amdgcn_s_setprio(0);
+    auto stream = [&](auto par, auto tail) {
+      drs_read_dma<T, PER_WAVE, decltype(par)::value, decltype(tail)::value>(
+          f, ad, dma, c.q_begin + (nst - 1) * kDrKR + dma.r_first, c.rows, voff);
+      mma();
       wait_vmcnt<0>();
       barrier_raw();
+    };
+    using P0 = std::integral_constant<int, 0>;
+    using P1 = std::integral_constant<int, 1>;
+    // the steady state streams the stages before the chunk's last: whole, real rows
+#pragma clang loop unroll(disable)
+    for (int n = nst - 2 + p0; n > 0; n -= 2) {
+      if (!skip) stream(P0{}, std::false_type{});
+      skip = false;
+      stream(P1{}, std::false_type{});
     }
-    for (; i < nst; ++i) {  // the last stage: nothing to stream
-      dr_read<T>(f, smem + (i & 1) * STAGE, c);
-      lds_barrier();
-      __builtin_amdgcn_s_setprio(1);
-      dr_mfma(acc, f);
-      __builtin_amdgcn_s_setprio(0);
+    if (nst >= 2) stream(P0{}, std::true_type{});  // streams the last stage
+    if (nst >= 1) {  // the last stage: nothing to stream
+      drs_read<T, 1>(f, ad);
+      mma();
       barrier_raw();
     }
     barrier_raw();
   } else {
     barrier_raw();
     // slot 2i+1: read stage i; slot 2i+2: MFMAs of stage i
-    for (int i = 0; i < nst; ++i) {
-      dr_read<T>(f, smem + (i & 1) * STAGE, c);
-      lds_barrier();
-      __builtin_amdgcn_s_setprio(1);
-      dr_mfma(acc, f);
-      __builtin_amdgcn_s_setprio(0);
+#pragma clang loop unroll(disable)
+    for (int n = nst + p0; n > 0; n -= 2) {
+      if (!skip) {
+        drs_read<T, 0>(f, ad);
+        mma();
+        barrier_raw();
+      }
+      skip = false;
+      drs_read<T, 1>(f, ad);
+      mma();
       barrier_raw();
     }
   }
