@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MPV_ABI_VERSION 14 /* 4: device-memory Philox keys (mpv_noise_philox*_dev);
+#define MPV_ABI_VERSION 15 /* 4: device-memory Philox keys (mpv_noise_philox*_dev);
                               5: T rows padded to roundup(L, 4) floats;
                               6: mpv_linear (the VAE's Linear layers); mpv_bwd_args
                                  dR64 and kl;
@@ -55,7 +55,10 @@ extern "C" {
                              13: mpv_calib_fwd / mpv_calib_bwd (post-process
                                  threshold calibration)
                              14: mpv_probit_predict (label-free prediction:
-                                 indiv_prob alone from a lean forward) */
+                                 indiv_prob alone from a lean forward)
+                             15: mpv_group_rows (the sensitive groups of a batch in
+                                 one launch), mpv_label_weights_batch (every
+                                 target table in one launch) */
 
 enum mpv_status { MPV_OK = 0, MPV_EINVAL = 1, MPV_ELAUNCH = 2 };
 enum mpv_dtype { MPV_F32 = 0, MPV_F64 = 1 };
@@ -463,8 +466,8 @@ int mpv_adam_finish(const mpv_adam_finish_args* args, void* stream);
  * HIP events on the launch stream (bench.py's per-kernel roofline timing).
  * Kernel names: noise_philox, probit_fwd, fwd_combine, finalize, bwd_coef,
  * bwd_elem, dR_gemm, sum_slabs, convert, bstat_combine, reparam_fwd,
- * reparam_bwd, kl_bwd, linear, adam, adam_finish, label_weights, fair_fwd,
- * fair_bwd, metrics, curve_keys, curve_sort (the LDS chunk sort), curve_merge
+ * reparam_bwd, kl_bwd, linear, adam, adam_finish, label_weights (mpv_label_weights and
+ * mpv_label_weights_batch), group_rows, fair_fwd, fair_bwd, metrics, curve_keys, curve_sort (the LDS chunk sort), curve_merge
  * (the merge passes), curve_pass, curve_agg, metric_sweep (every launch of
  * mpv_threshold_sweep), calib_fwd, calib_tables, calib_bwd, probit_predict,
  * predict_final (the two launches of mpv_probit_predict).  Query synchronises
@@ -494,6 +497,41 @@ typedef struct mpv_label_table {
  * int()); *contributed += #rows with w > 0 (fairsoft_train.py:91-92). */
 int mpv_label_weights(const float* y, int64_t B, int64_t L, const mpv_label_table* table,
                       double* w, int32_t* contributed, void* stream);
+
+/* mpv_label_weights for T target tables (a host array of T structs) at once:
+ * w is (T, B), row t what mpv_label_weights gives for tables[t], and
+ * *contributed grows by the sum of the T counts -- bit for bit what T calls
+ * give.  The tables go to the kernel by value, MPV_LABEL_TABLES_PER_LAUNCH per
+ * launch (T <= 8 is one launch); a row is packed and hashed once per launch
+ * and probed in each of its tables.  Every table needs W == ceil(L / 64)
+ * (else MPV_EINVAL, before any launch); one with nslots == 0 gives weight 0. */
+#define MPV_LABEL_TABLES_PER_LAUNCH 8
+int mpv_label_weights_batch(const float* y, int64_t B, int64_t L, const mpv_label_table* tables,
+                            int64_t T, double* w /* (T, B) */, int32_t* contributed,
+                            void* stream);
+
+/* The sensitive groups of a batch (fairsoft_train.py:81 torch.unique(x, dim=0)
+ * and the row masks of :106-111) in one launch of one workgroup.  x is (B, n)
+ * row-major of element type x_elem, read as it is (no cast launch).
+ *   r(b)      = number of distinct rows of x that sort lexicographically
+ *               before row b: the row's index in torch.unique(x, dim=0).
+ *               Elements compare by value (-0.0 equals +0.0); the result for a
+ *               NaN element is unspecified.
+ *   *overflow = any r(b) >= G, one 0 / 1 byte
+ *   gid[b]    = min(r(b), G - 1)
+ *   order     (B) the row indices sorted by gid, ties by row index
+ *   goff[k]   (G + 1) = number of rows with gid < k
+ * -- the gid / order / goff of mpv_fair_args.  O(B^2 n) compares in loops of a
+ * fixed order; x is staged in LDS when it fits (B n elements in 40 KiB), read
+ * from global memory otherwise.
+ * Supported: 1 <= B <= MPV_GROUP_MAX_B, 1 <= n <= MPV_GROUP_MAX_N,
+ * 1 <= G <= MPV_GROUP_MAX_B (G may exceed B: the slots past the batch's groups
+ * stay empty); anything else is MPV_EINVAL and launches nothing. */
+enum mpv_elem { MPV_EL_F32 = 0, MPV_EL_F64 = 1, MPV_EL_I32 = 2, MPV_EL_I64 = 3 };
+#define MPV_GROUP_MAX_B 4096
+#define MPV_GROUP_MAX_N 64
+int mpv_group_rows(const void* x, int x_elem, int64_t B, int64_t n, int64_t G, int32_t* gid,
+                   int32_t* order, int32_t* goff, uint8_t* overflow, void* stream);
 
 enum mpv_fair_norm { MPV_FAIR_L1 = 1, MPV_FAIR_L2 = 2 };
 

@@ -8,6 +8,12 @@
 //                          table of packed patterns (built once on the host
 //                          from the same dict), instead of a Python string join
 //                          and dict lookup per row.
+//   label_weights_batch_   the same for up to MPV_LABEL_TABLES_PER_LAUNCH target
+//   kernel                 tables in one launch: the row packed and hashed once.
+//   group_rows_kernel      the batch's sensitive groups (torch.unique(x, dim=0)'s
+//                          inverse, fairsoft_train.py:81, :106-111) with the
+//                          stable order by group and the group offsets, in one
+//                          launch of one workgroup.
 //   fair_fwd_kernel        the fairness regulariser (fairsoft_train.py:95-131):
 //                          weighted means of indiv_prob_label / indiv_prob over
 //                          the batch and over each sensitive group, l1 or l2
@@ -43,6 +49,43 @@ MPV_DEV uint64_t mix64(uint64_t z) {
 // 64w + j of the reference's key string).  A row with a label value whose
 // int() is neither 0 nor 1 has no binary key: weight 0, as a dict miss.
 constexpr int kLwWaves = 4;
+
+// Row b's pattern into words[0..W) (this wave's LDS row) and its hash; true
+// when the row has no binary key.
+MPV_DEV bool pack_row(const float* __restrict__ y, int b, int L, int W, uint64_t* words,
+                      uint64_t& h) {
+  const int lane = threadIdx.x & 63;
+  bool bad = false;
+  h = 0x6A09E667F3BCC909ull ^ (uint64_t)W;
+  for (int k = 0; k < W; ++k) {
+    const int l = k * 64 + lane;
+    const float v = l < L ? truncf(y[(int64_t)b * L + l]) : 0.0f;
+    bad |= !(v == 0.0f || v == 1.0f);
+    const uint64_t bits = __ballot(v == 1.0f);
+    if (lane == 0) words[k] = bits;
+    h = mix64(h ^ bits);
+  }
+  bad = __any(bad);
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  return bad;
+}
+
+// The table's value for the packed row (0 when absent), the whole wave probing.
+MPV_DEV double probe_table(const mpv_label_table& tab, uint64_t h, const uint64_t* words) {
+  const int lane = threadIdx.x & 63, W = (int)tab.W;
+  if (tab.nslots <= 0) return 0.0;
+  const uint64_t mask = (uint64_t)tab.nslots - 1;
+  for (uint64_t probe = 0; probe < (uint64_t)tab.nslots; ++probe) {
+    const uint64_t slot = (h + probe) & mask;
+    if (!tab.used[slot]) break;  // empty slot: not in the table
+    bool diff = false;
+    for (int k = lane; k < W; k += 64) diff |= tab.keys[slot * W + k] != words[k];
+    if (!__any(diff)) return tab.vals[slot];
+  }
+  return 0.0;
+}
+
 __global__ __launch_bounds__(64 * kLwWaves) void label_weights_kernel(
     const float* __restrict__ y, int B, int L, mpv_label_table tab, double* __restrict__ w,
     int* __restrict__ contributed) {
@@ -50,38 +93,112 @@ __global__ __launch_bounds__(64 * kLwWaves) void label_weights_kernel(
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int b = blockIdx.x * kLwWaves + wv;
   if (b >= B) return;
-  const int W = (int)tab.W;
-  bool bad = false;
-  uint64_t h = 0x6A09E667F3BCC909ull ^ (uint64_t)W;
-  for (int k = 0; k < W; ++k) {
-    const int l = k * 64 + lane;
-    const float v = l < L ? truncf(y[(int64_t)b * L + l]) : 0.0f;
-    bad |= !(v == 0.0f || v == 1.0f);
-    const uint64_t bits = __ballot(v == 1.0f);
-    if (lane == 0) words[wv][k] = bits;
-    h = mix64(h ^ bits);
-  }
-  bad = __any(bad);
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  double val = 0.0;
-  if (!bad && tab.nslots > 0) {
-    const uint64_t mask = (uint64_t)tab.nslots - 1;
-    for (uint64_t probe = 0; probe < (uint64_t)tab.nslots; ++probe) {
-      const uint64_t slot = (h + probe) & mask;
-      if (!tab.used[slot]) break;  // empty slot: not in the table
-      bool diff = false;
-      for (int k = lane; k < W; k += 64) diff |= tab.keys[slot * W + k] != words[wv][k];
-      if (!__any(diff)) {
-        val = tab.vals[slot];
-        break;
-      }
-    }
-  }
+  uint64_t h;
+  const bool bad = pack_row(y, b, L, (int)tab.W, words[wv], h);
+  const double val = bad ? 0.0 : probe_table(tab, h, words[wv]);
   if (lane == 0) {
     w[b] = val;
     if (val > 0.0) atomicAdd(contributed, 1);  // integer count: order-free
   }
+}
+
+// Up to MPV_LABEL_TABLES_PER_LAUNCH target tables by value: the row is packed
+// and hashed once, then probed in every table (w row t of this chunk).
+struct LabelTables {
+  mpv_label_table t[MPV_LABEL_TABLES_PER_LAUNCH];
+  int n;
+};
+
+__global__ __launch_bounds__(64 * kLwWaves) void label_weights_batch_kernel(
+    const float* __restrict__ y, int B, int L, LabelTables tabs, double* __restrict__ w,
+    int* __restrict__ contributed) {
+  __shared__ uint64_t words[kLwWaves][64];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int b = blockIdx.x * kLwWaves + wv;
+  if (b >= B) return;
+  uint64_t h;
+  const bool bad = pack_row(y, b, L, (int)tabs.t[0].W, words[wv], h);
+  int positive = 0;
+  for (int t = 0; t < tabs.n; ++t) {
+    const double val = bad ? 0.0 : probe_table(tabs.t[t], h, words[wv]);
+    if (lane == 0) w[(int64_t)t * B + b] = val;
+    positive += val > 0.0;
+  }
+  if (lane == 0 && positive) atomicAdd(contributed, positive);  // integer count: order-free
+}
+
+// ------------------------------------------------------------- row grouping
+// torch.unique(x, dim=0)'s inverse with the group layout mpv_fair_args wants,
+// in one workgroup: every row's rank among the distinct rows, then its place
+// in the stable order by group.  O(B^2 n) compares on integers in loops of a
+// fixed order; the rows sit in LDS when they fit.
+constexpr int kGroupThreads = 1024;
+constexpr int kGroupStageBytes = 40960;  // + 20 KiB of static LDS below: under 64 KiB
+
+// < 0, 0, > 0: row a sorts before, equals, sorts after row b; by value, so
+// -0.0 equals +0.0
+template <typename T>
+MPV_DEV int row_cmp(const T* a, const T* b, int n) {
+  for (int j = 0; j < n; ++j) {
+    const T u = a[j], v = b[j];
+    if (u != v) return u < v ? -1 : 1;
+  }
+  return 0;
+}
+
+template <typename T>
+__global__ __launch_bounds__(kGroupThreads) void group_rows_kernel(
+    const T* __restrict__ x, int B, int n, int G, int stage, int* __restrict__ gid,
+    int* __restrict__ order, int* __restrict__ goff, uint8_t* __restrict__ overflow) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char group_stage[];
+  __shared__ int s_gid[MPV_GROUP_MAX_B];
+  __shared__ uint8_t s_first[MPV_GROUP_MAX_B];
+  __shared__ int s_over;
+  const int tid = threadIdx.x, nt = blockDim.x;
+  const T* rows = x;
+  if (stage) {
+    T* s = reinterpret_cast<T*>(group_stage);
+    for (int i = tid; i < B * n; i += nt) s[i] = x[i];
+    rows = s;
+  }
+  if (tid == 0) s_over = 0;
+  __syncthreads();
+  // row b is the first occurrence of its pattern: no earlier identical row
+  for (int b = tid; b < B; b += nt) {
+    int c = 0;
+    while (c < b && row_cmp(rows + c * n, rows + b * n, n) != 0) ++c;
+    s_first[b] = c == b;
+  }
+  __syncthreads();
+  // r(b) = distinct rows that sort before row b
+  for (int b = tid; b < B; b += nt) {
+    int r = 0;
+    for (int c = 0; c < B; ++c)
+      if (s_first[c] && row_cmp(rows + c * n, rows + b * n, n) < 0) ++r;
+    if (r >= G) {
+      s_over = 1;  // every writer stores the same value
+      r = G - 1;
+    }
+    s_gid[b] = r;
+    gid[b] = r;
+  }
+  __syncthreads();
+  // the stable argsort by group: rows of a smaller group, then earlier rows of this one
+  for (int b = tid; b < B; b += nt) {
+    const int k = s_gid[b];
+    int pos = 0;
+    for (int c = 0; c < B; ++c) {
+      const int kc = s_gid[c];
+      pos += (kc < k || (kc == k && c < b)) ? 1 : 0;
+    }
+    order[pos] = b;
+  }
+  for (int k = tid; k <= G; k += nt) {
+    int below = 0;
+    for (int c = 0; c < B; ++c) below += s_gid[c] < k ? 1 : 0;
+    goff[k] = below;
+  }
+  if (tid == 0) *overflow = s_over ? 1 : 0;
 }
 
 // -------------------------------------------------------- fairness penalty
@@ -346,21 +463,83 @@ __global__ void metric_final_kernel(const double* __restrict__ rowstat,
 
 using namespace mpv;
 
-extern "C" {
-
-int mpv_label_weights(const float* y, int64_t B, int64_t L, const mpv_label_table* tab,
-                      double* w, int32_t* contributed, void* stream) {
-  MPV_REQUIRE(y && tab && w && contributed && B > 0 && L > 0, "bad label_weights arguments");
+static int check_label_table(const mpv_label_table* tab, int64_t L) {
   MPV_REQUIRE(tab->W == (L + 63) / 64, "table words %lld != ceil(L/64) = %lld",
               (long long)tab->W, (long long)((L + 63) / 64));
   MPV_REQUIRE(tab->nslots == 0 || (tab->keys && tab->vals && tab->used &&
                                    (tab->nslots & (tab->nslots - 1)) == 0),
               "table slots must be a power of two with keys/vals/used");
   MPV_REQUIRE(tab->W <= 64, "label_dim > 4096 is not supported by the pattern table");
+  return MPV_OK;
+}
+
+template <typename T>
+static void launch_group_rows(const void* x, int B, int n, int G, int32_t* gid, int32_t* order,
+                              int32_t* goff, uint8_t* overflow, hipStream_t st) {
+  const size_t bytes = sizeof(T) * (size_t)B * n;
+  const int stage = bytes <= (size_t)kGroupStageBytes;
+  const int threads = B >= kGroupThreads ? kGroupThreads : (int)align_up(B, 64);
+  MPV_LAUNCH("group_rows", group_rows_kernel<T>, dim3(1), dim3(threads), stage ? bytes : 0, st,
+             static_cast<const T*>(x), B, n, G, stage, gid, order, goff, overflow);
+}
+
+extern "C" {
+
+int mpv_label_weights(const float* y, int64_t B, int64_t L, const mpv_label_table* tab,
+                      double* w, int32_t* contributed, void* stream) {
+  MPV_REQUIRE(y && tab && w && contributed && B > 0 && L > 0, "bad label_weights arguments");
+  if (int rc = check_label_table(tab, L)) return rc;
   const int blocks = (int)cdiv(B, kLwWaves);
   MPV_LAUNCH("label_weights", label_weights_kernel, dim3(blocks), dim3(64 * kLwWaves), 0,
              as_stream(stream), y, (int)B, (int)L, *tab, w, contributed);
   return check_launch("label_weights");
+}
+
+int mpv_label_weights_batch(const float* y, int64_t B, int64_t L, const mpv_label_table* tables,
+                            int64_t T, double* w, int32_t* contributed, void* stream) {
+  MPV_REQUIRE(y && tables && w && contributed && B > 0 && L > 0 && T > 0,
+              "bad label_weights_batch arguments");
+  for (int64_t t = 0; t < T; ++t)  // every table is checked before the first launch
+    if (int rc = check_label_table(tables + t, L)) return rc;
+  const int blocks = (int)cdiv(B, kLwWaves);
+  for (int64_t t0 = 0; t0 < T; t0 += MPV_LABEL_TABLES_PER_LAUNCH) {
+    LabelTables tabs;
+    tabs.n = (int)(T - t0 < MPV_LABEL_TABLES_PER_LAUNCH ? T - t0 : MPV_LABEL_TABLES_PER_LAUNCH);
+    for (int i = 0; i < MPV_LABEL_TABLES_PER_LAUNCH; ++i)
+      tabs.t[i] = tables[t0 + (i < tabs.n ? i : 0)];
+    MPV_LAUNCH("label_weights", label_weights_batch_kernel, dim3(blocks), dim3(64 * kLwWaves), 0,
+               as_stream(stream), y, (int)B, (int)L, tabs, w + t0 * B, contributed);
+    if (int rc = check_launch("label_weights_batch")) return rc;
+  }
+  return MPV_OK;
+}
+
+int mpv_group_rows(const void* x, int x_elem, int64_t B, int64_t n, int64_t G, int32_t* gid,
+                   int32_t* order, int32_t* goff, uint8_t* overflow, void* stream) {
+  MPV_REQUIRE(x && gid && order && goff && overflow, "NULL pointer in mpv_group_rows");
+  MPV_REQUIRE(B >= 1 && B <= MPV_GROUP_MAX_B && n >= 1 && n <= MPV_GROUP_MAX_N && G >= 1 &&
+                  G <= MPV_GROUP_MAX_B,
+              "mpv_group_rows supports 1 <= B, G <= %d and 1 <= n <= %d (got B %lld, n %lld, "
+              "G %lld)", MPV_GROUP_MAX_B, MPV_GROUP_MAX_N, (long long)B, (long long)n,
+              (long long)G);
+  hipStream_t st = as_stream(stream);
+  switch (x_elem) {
+    case MPV_EL_F32:
+      launch_group_rows<float>(x, (int)B, (int)n, (int)G, gid, order, goff, overflow, st);
+      break;
+    case MPV_EL_F64:
+      launch_group_rows<double>(x, (int)B, (int)n, (int)G, gid, order, goff, overflow, st);
+      break;
+    case MPV_EL_I32:
+      launch_group_rows<int32_t>(x, (int)B, (int)n, (int)G, gid, order, goff, overflow, st);
+      break;
+    case MPV_EL_I64:
+      launch_group_rows<int64_t>(x, (int)B, (int)n, (int)G, gid, order, goff, overflow, st);
+      break;
+    default:
+      return fail(MPV_EINVAL, "mpv_group_rows: unknown element type %d", x_elem);
+  }
+  return check_launch("group_rows");
 }
 
 size_t mpv_fair_workspace_bytes(int64_t L, int64_t T, int64_t G) {

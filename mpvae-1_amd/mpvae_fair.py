@@ -11,7 +11,12 @@
   0.5, all_metrics=False)`` (evals.py:178-238, used at fairsoft_train.py:149-153).
 
 Both run in libmpvae_hip.so (csrc/fairness.hip) behind the C ABI; there is no
-host fallback.  Differences from the reference, none of them numeric:
+host fallback.  ``fairness_penalty(..., fused=True)`` takes the row weights of
+every target table from one launch (``label_weights_batch``) and the batch's
+sensitive groups from one launch (``group_rows``) where the default path
+launches once per table and builds the groups from torch ops
+(``sensitive_groups``); the results are equal bit for bit.
+Differences from the reference, none of them numeric:
 * the reference returns the Python float 0. when no target/group term is
   active (and then does not add it); ``fairness_penalty`` returns a zero
   fp64 tensor instead, which adds nothing -- deciding "float or tensor" would
@@ -159,6 +164,28 @@ def label_weights(labels, tables):
     return w, count
 
 
+def label_weights_batch(labels, tables):
+    """``label_weights`` with every target table in one launch per
+    ``H.LABEL_TABLES_PER_LAUNCH`` tables (mpv_label_weights_batch): each row is
+    packed and hashed once, then looked up in every table.  The same ``(w,
+    count)``, bit for bit."""
+    H.require_gpu(labels)
+    y = labels.contiguous().float()
+    B, L = y.shape
+    w = torch.empty((len(tables), B), dtype=torch.float64, device=y.device)
+    count = torch.zeros((), dtype=torch.int32, device=y.device)
+    if B == 0 or not tables:  # nothing to look up: no launch with an empty grid
+        return w, count
+    for tab in tables:
+        if tab.L != L:
+            raise ValueError(f"table built for label_dim {tab.L}, labels have {L}")
+    structs = (H.LabelTable * len(tables))(*[tab.c_struct() for tab in tables])
+    H.check(H.load_library().mpv_label_weights_batch(H.ptr(y), B, L, structs, len(tables), H.ptr(w),
+                                                     H.ptr(count), H.stream_of(y.device)),
+            "mpv_label_weights_batch")
+    return w, count
+
+
 def group_ids(sensitive_feat):
     """Row b's index in ``torch.unique(sensitive_feat, dim=0)`` (the reference's
     group order, fairsoft_train.py:80, :103-104), from fixed-size tensor ops:
@@ -204,6 +231,47 @@ def sensitive_groups(sensitive_feat, max_groups=None):
     goff = torch.zeros(G + 1, dtype=torch.int32, device=gid.device)
     goff[1:] = torch.cumsum(counts, 0).to(torch.int32)
     return gid.contiguous(), order.contiguous(), goff, G, overflow
+
+
+_ELEMS = {torch.float32: H.EL_F32, torch.float64: H.EL_F64, torch.int32: H.EL_I32,
+          torch.int64: H.EL_I64}
+
+
+def group_rows(sensitive_feat, max_groups=None):
+    """``sensitive_groups(sensitive_feat, max_groups)`` in one launch
+    (mpv_group_rows): the same ``(gid, order, goff, G, overflow)``, equal
+    element for element.  fp32 / fp64 / int32 / int64 features are read as they
+    are (``torch.from_numpy(data.sensitive_feat[idx])`` is int64 or float64);
+    any other dtype is cast once, to int64 if integral or bool, to float32
+    otherwise.  A shape outside the kernel's range (more than
+    ``H.GROUP_MAX_B`` rows or group slots, more than ``H.GROUP_MAX_N``
+    columns) goes through ``sensitive_groups``.  No host sync."""
+    H.require_gpu(sensitive_feat)
+    B = sensitive_feat.shape[0]
+    G = int(max_groups) if max_groups is not None else max(B, 1)
+    if G < 1:
+        raise ValueError(f"max_groups must be >= 1 (got {max_groups})")
+    dev = sensitive_feat.device
+    if B == 0:  # no row to group: no launch (group_ids' guard)
+        return (torch.zeros(0, dtype=torch.int32, device=dev),
+                torch.zeros(0, dtype=torch.int32, device=dev),
+                torch.zeros(G + 1, dtype=torch.int32, device=dev), G,
+                torch.zeros((), dtype=torch.bool, device=dev))
+    x = sensitive_feat.reshape(B, -1)
+    if x.dtype not in _ELEMS:
+        x = x.to(torch.float32 if x.dtype.is_floating_point else torch.int64)
+    x = x.contiguous()
+    gid = torch.empty(B, dtype=torch.int32, device=dev)
+    order = torch.empty(B, dtype=torch.int32, device=dev)
+    goff = torch.empty(G + 1, dtype=torch.int32, device=dev)
+    overflow = torch.empty((), dtype=torch.bool, device=dev)
+    rc = H.load_library().mpv_group_rows(H.ptr(x), _ELEMS[x.dtype], B, x.shape[1], G, H.ptr(gid),
+                                         H.ptr(order), H.ptr(goff), H.ptr(overflow),
+                                         H.stream_of(dev))
+    if rc == H.EINVAL:  # outside the kernel's range: nothing was launched
+        return sensitive_groups(sensitive_feat, max_groups)
+    H.check(rc, "mpv_group_rows")
+    return gid, order, goff, G, overflow
 
 
 class _FairPenalty(torch.autograd.Function):
@@ -254,7 +322,7 @@ NORMS = {"l1": H.FAIR_L1, "l2": H.FAIR_L2}
 
 
 def fairness_penalty(indiv_prob_label, indiv_prob, input_label, sensitive_feat, tables,
-                     fairness_loss_norm, fair_coeff, max_groups=None):
+                     fairness_loss_norm, fair_coeff, max_groups=None, *, fused=False):
     """fairsoft_train.py:75-131 on the device.
 
     indiv_prob_label, indiv_prob -- compute_loss outputs 8 and 7 (label_z, feat_z)
@@ -266,6 +334,12 @@ def fairness_penalty(indiv_prob_label, indiv_prob, input_label, sensitive_feat, 
                                      patterns in a batch (default: the batch size;
                                      a batch with more distinct patterns than the
                                      bound makes the penalty NaN)
+    fused                         -- the row weights and the groups from one launch
+                                     each (``label_weights_batch``, ``group_rows``)
+                                     instead of one launch per table and the
+                                     torch ops of ``sensitive_groups``: the same
+                                     integers and weights, so the same loss and
+                                     gradients bit for bit
     No host sync: the call (forward and backward) can be captured in a HIP
     graph (tests/test_gpu_fair.py).
     Returns ``(fairloss, contributed)``: fairloss is a differentiable 0-d
@@ -280,8 +354,9 @@ def fairness_penalty(indiv_prob_label, indiv_prob, input_label, sensitive_feat, 
         # shapes and len(tables) are host knowledge: no sync, still capturable
         count = torch.zeros((), dtype=torch.int32, device=indiv_prob_label.device)
         return _ZeroPenalty.apply(indiv_prob_label, indiv_prob), count
-    w, count = label_weights(input_label, tables)
-    gid, order, goff, G, overflow = sensitive_groups(sensitive_feat, max_groups)
+    w, count = (label_weights_batch if fused else label_weights)(input_label, tables)
+    gid, order, goff, G, overflow = (group_rows if fused else sensitive_groups)(sensitive_feat,
+                                                                                max_groups)
     norm = NORMS.get(fairness_loss_norm, 0)
     loss = _FairPenalty.apply(indiv_prob_label, indiv_prob, w, gid, order, goff, G, norm,
                               fair_coeff)

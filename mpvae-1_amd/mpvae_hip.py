@@ -13,7 +13,7 @@ import torch  # noqa: F401  (must precede the .so load: one HIP runtime per proc
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MPVAE_HIP_LIB", os.path.join(HERE, "libmpvae_hip.so"))
 
-ABI_VERSION = 14
+ABI_VERSION = 15
 F32, F64 = 0, 1
 G_TOTAL, G_NLL, G_NLL_X, G_C, G_C_X, G_KL = range(6)
 
@@ -99,6 +99,10 @@ class LabelTable(ctypes.Structure):
 
 
 FAIR_L1, FAIR_L2 = 1, 2
+LABEL_TABLES_PER_LAUNCH = 8  # MPV_LABEL_TABLES_PER_LAUNCH
+EL_F32, EL_F64, EL_I32, EL_I64 = range(4)  # mpv_elem
+GROUP_MAX_B, GROUP_MAX_N = 4096, 64  # mpv_group_rows' supported range
+EINVAL = 1
 
 
 class LinearArgs(ctypes.Structure):
@@ -216,6 +220,11 @@ SIGNATURES = {
                                         ctypes.POINTER(ctypes.c_double)]),
     "mpv_label_weights": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.c_int64,
                                          ctypes.POINTER(LabelTable), vp, vp, vp]),
+    "mpv_label_weights_batch": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.c_int64,
+                                               ctypes.POINTER(LabelTable), ctypes.c_int64, vp, vp,
+                                               vp]),
+    "mpv_group_rows": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
+                                      ctypes.c_int64, vp, vp, vp, vp, vp]),
     "mpv_fair_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64,
                                                    ctypes.c_int64]),
     "mpv_fair_fwd": (ctypes.c_int, [ctypes.POINTER(FairArgs), vp, ctypes.c_size_t, vp]),
@@ -296,7 +305,7 @@ def require_gpu(*tensors):
 
 KERNELS = ["noise_philox", "split", "probit_fwd", "fwd_combine", "finalize", "bwd_coef", "bwd_elem",
            "dR_gemm", "sum_slabs", "convert", "bstat_combine", "reparam_fwd", "reparam_bwd",
-           "kl_bwd", "label_weights", "fair_fwd", "fair_bwd", "metrics", "linear", "adam",
+           "kl_bwd", "label_weights", "group_rows", "fair_fwd", "fair_bwd", "metrics", "linear", "adam",
            "adam_finish", "curve_keys", "curve_sort", "curve_merge", "curve_pass", "curve_agg",
            "metric_sweep", "calib_fwd", "calib_tables", "calib_bwd", "probit_predict",
            "predict_final"]

@@ -16,6 +16,7 @@ fairsoft_train.py:154-162).  Each sync drains the stream.  Here:
 Both are torch glue around the loop, not kernels of the hot path: they run on
 whatever device the tensors live on.
 """
+import collections
 import copy
 import ctypes
 import functools
@@ -310,20 +311,30 @@ class TrainStep:
         for dt, grads in by_dtype.items():
             torch._foreach_mul_(grads, coef.to(dt))
 
-    def _body(self, label, feat):
-        import mpvae
-        self.opt.zero_grad(set_to_none=True)
-        seed = getattr(self.args, "mpvae_seed", None)
+    def _step_args(self):
+        """``args`` for one step's compute_loss: with a device seed, fresh probit
+        noise every step, on the device -- compute_loss's finalize launch
+        advances the key after the noise has read it (args.mpvae_seed_advance;
+        no launch of its own)."""
         args = self.args
-        if self.advance_seed and isinstance(seed, torch.Tensor):
-            # fresh probit noise every step, on the device: compute_loss's
-            # finalize launch advances the key after the noise has read it
-            # (args.mpvae_seed_advance; no launch of its own)
+        if self.advance_seed and isinstance(getattr(args, "mpvae_seed", None), torch.Tensor):
             args = copy.copy(self.args)
             args.mpvae_seed_advance = True
+        return args
+
+    def _objective(self, label, feat):
+        """Forward and loss: ``(the tensor to backpropagate, the step's
+        outputs)``.  Here compute_loss's total and its 8 outputs; a subclass
+        adds its terms (FairTrainStep)."""
+        import mpvae
         out = self.model(label, feat)
-        res = mpvae.compute_loss(label, *out, self.model.r_sqrt_sigma, args)
-        res[0].backward()
+        res = mpvae.compute_loss(label, *out, self.model.r_sqrt_sigma, self._step_args())
+        return res[0], res
+
+    def _body(self, label, feat):
+        self.opt.zero_grad(set_to_none=True)
+        objective, res = self._objective(label, feat)
+        objective.backward()
         self._clip()
         # finite gate: the AMP multi-tensor check (one launch per dtype) sets
         # found_inf if any gradient holds a NaN / inf; its unscale by 1.0
@@ -457,10 +468,7 @@ class CalibrationStep(TrainStep):
         import mpvae
         import mpvae_fair
         self.opt.zero_grad(set_to_none=True)
-        args = self.args
-        if isinstance(getattr(args, "mpvae_seed", None), torch.Tensor):
-            args = copy.copy(self.args)  # fresh probit noise every step (TrainStep._body)
-            args.mpvae_seed_advance = True
+        args = self._step_args()
         with torch.no_grad():
             out = self.model(label, feat)
             res = mpvae.compute_loss(label, *out, self.model.r_sqrt_sigma, args)
@@ -491,3 +499,174 @@ class CalibrationStep(TrainStep):
         static buffer."""
         self.sens = sensitive_feat.clone()
         return super().capture(label, feat, warmup)
+
+
+FairStepOut = collections.namedtuple(
+    "FairStepOut", ["total", "nll", "nll_x", "c", "c_x", "kl", "indiv_prob", "indiv_prob_label",
+                    "fairloss", "contributed", "metrics"])
+# the running sums FairTrainStep keeps (the reference's smooth_* accumulators)
+SUM_KEYS = ["total", "nll", "nll_x", "c", "c_x", "kl", "fairloss", "maF1", "miF1"]
+
+
+class _Totals:
+    """Device accumulators of one loop (training or validation): the fp64 sums
+    of SUM_KEYS, the step count and the int64 contributed count."""
+
+    def __init__(self, dev):
+        import mpvae_fair
+        self.sums = torch.zeros(len(SUM_KEYS), dtype=torch.float64, device=dev)
+        self.counts = torch.zeros(2, dtype=torch.int64, device=dev)  # steps, contributed
+        self._one = torch.ones((), dtype=torch.int64, device=dev)
+        self._f1 = torch.tensor([mpvae_fair.METRIC_KEYS.index("maF1"),
+                                 mpvae_fair.METRIC_KEYS.index("miF1")], device=dev)
+
+    def add(self, out):
+        losses = torch.stack([t.detach() for t in out[:6]]).to(torch.float64)
+        self.sums += torch.cat([losses, out.fairloss.to(torch.float64).reshape(1),
+                                out.metrics[self._f1]])
+        self.counts += torch.stack([self._one, out.contributed.to(torch.int64)])
+
+    def zero_(self):
+        self.sums.zero_()
+        self.counts.zero_()
+
+
+class FairTrainStep(TrainStep):
+    """The loop body of train_mpvae_softfair_one_epoch with ``penalize_unfair``
+    (fairsoft_train.py:47-162) as one call: TrainStep's step with the fairness
+    regulariser in the objective -- ``model(label, feat)`` -> ``compute_loss``
+    -> ``mpvae_fair.fairness_penalty(fused=True)`` -> backward of total +
+    fairloss -> clip -> finite-gradient gate -> Adam -> StepLR -> the per-step
+    train metrics (after the update, :149-152) -> the running sums, all on the
+    device.
+
+    ``step(label, feat, sensitive_feat)`` returns a ``FairStepOut``:
+    compute_loss's eight outputs, ``fairloss``, ``contributed`` (int32) and
+    ``metrics`` ((8,) fp64 in ``mpvae_fair.METRIC_KEYS`` order).  ``total`` is
+    fp32 and equals float32(float64(compute_loss's total) + fairloss), as the
+    reference's in-place ``total_loss += fairloss`` (:137); the backward runs
+    on the unrounded sum.  ``tables`` are the ``LabelDistanceTable``s of the
+    target fair labels; ``[]`` is the reference's ``penalize_unfair=0``.
+    ``args`` is TrainStep's namespace plus ``fair_coeff`` and
+    ``fairness_loss_norm``; ``max_groups`` as in ``fairness_penalty`` -- a
+    batch with more sensitive patterns than the bound makes the penalty NaN
+    and the gate skips the update.
+
+    In place of the reference's eight ``.item()`` calls per step and its
+    ``contributed_reg_fair_sample`` (:154-173) the step adds to device sums
+    (SUM_KEYS, a step count, ``contributed``) on every step, whether or not the
+    gate skipped the update; ``read_totals()`` is the only host sync.
+    ``validate()`` is the body of validate_mpvae_softfair with sums of its own.
+
+    Differences from the reference:
+    * r_sqrt_sigma is the model's (the ``residue_sigma == "random"`` per-step
+      host draw is not reproduced, as in TrainStep);
+    * ``fairloss`` is always a tensor, zero when no term is active (the
+      reference's Python float 0., which it does not add);
+    * the penalty arithmetic is fp64 whatever the distance values are
+      (mpvae_fair's module docstring).
+
+    With Philox noise and a device seed nothing in ``step`` waits for the
+    host; ``capture()`` records it, sums included, in one HIP graph."""
+
+    # fairness_penalty's flag; False (set on an instance before capture) is the
+    # unfused penalty, bit for bit the same step: tools/bench_fair_step.py's yardstick
+    fused = True
+
+    def __init__(self, model, optimizer, args, tables, max_groups=None, scheduler=None):
+        super().__init__(model, optimizer, args, scheduler=scheduler)
+        self.tables, self.max_groups = list(tables), max_groups
+        self.sens = None
+        dev = self.params[0].device
+        self.totals, self.valid_totals = _Totals(dev), _Totals(dev)
+
+    def _forward(self, label, feat, norm):
+        """Forward, loss, penalty: (the unrounded total + fairloss, a
+        FairStepOut without its metrics)."""
+        import mpvae
+        import mpvae_fair
+        out = self.model(label, feat)
+        res = mpvae.compute_loss(label, *out, self.model.r_sqrt_sigma, self._step_args())
+        fair, contributed = mpvae_fair.fairness_penalty(
+            res[7], res[6], label, self.sens, self.tables, norm, self.args.fair_coeff,
+            max_groups=self.max_groups, fused=self.fused)
+        objective = res[0].to(torch.float64) + fair
+        if self.tables and self.max_groups is not None:
+            # a batch with more patterns than the bound: the penalty is NaN but
+            # its gradients are zero; scaling by 1 (NaN in that case) hands
+            # the gate NaN gradients, and changes no bit otherwise
+            nan_or_zero = fair.detach() - fair.detach()
+            objective = objective * (1.0 + nan_or_zero)
+        return objective, FairStepOut(objective.detach().float(), *res[1:], fair.detach(),
+                                      contributed, None)
+
+    def _with_metrics(self, out, label, totals):
+        import mpvae_fair
+        metrics = mpvae_fair._train_metrics(out.indiv_prob.detach().contiguous().float(),
+                                            label.contiguous().float(), 0.5)
+        out = out._replace(metrics=metrics)
+        totals.add(out)
+        return out
+
+    def _objective(self, label, feat):
+        return self._forward(label, feat, self.args.fairness_loss_norm)
+
+    def _body(self, label, feat):
+        return self._with_metrics(super()._body(label, feat), label, self.totals)
+
+    def __call__(self, label, feat, sensitive_feat):
+        """One step (a replay once captured) on the batch."""
+        if self.graph is not None:
+            self.sens.copy_(sensitive_feat)
+        else:
+            self.sens = sensitive_feat
+        return super().__call__(label, feat)
+
+    step = __call__
+
+    def capture(self, label, feat, sensitive_feat, warmup=2):
+        """TrainStep.capture with the batch's sensitive features as a third
+        static buffer."""
+        self.sens = sensitive_feat.clone()
+        return super().capture(label, feat, warmup)
+
+    def validate(self, label, feat, sensitive_feat):
+        """The loop body of validate_mpvae_softfair (fairsoft_train.py:234-331)
+        on one batch: ``model.eval()`` and ``no_grad``, the same forward, loss,
+        penalty and metrics, no backward and no update; a ``FairStepOut``,
+        added to the validation sums.  The reference's validation penalty
+        always squares (:305-308), whatever ``fairness_loss_norm`` says, so
+        the norm here is "l2".  The model's train / eval mode is restored.
+        Runs eagerly: it is not part of a captured graph."""
+        was_training, sens = self.model.training, self.sens
+        self.model.eval()
+        self.sens = sensitive_feat
+        try:
+            with torch.no_grad():
+                _, out = self._forward(label, feat, "l2")
+                return self._with_metrics(out, label, self.valid_totals)
+        finally:
+            self.sens = sens
+            self.model.train(was_training)
+
+    def read_totals(self, reset=True):
+        """The running sums as Python numbers, with one host sync: the SUM_KEYS
+        sums (divide by ``steps`` for the reference's running_postfix),
+        ``steps``, ``contributed`` and ``updates`` of the training steps, and
+        under ``"valid"`` the same (without ``updates``) of the ``validate``
+        calls.  ``reset`` zeroes the sums, step counts and contributed counts
+        (``updates`` keeps counting, as TrainStep's)."""
+        t, v = self.totals, self.valid_totals
+        vals = torch.cat([t.sums, v.sums,
+                          torch.cat([t.counts, v.counts, self.updates.reshape(1)])
+                          .to(torch.float64)]).tolist()
+        n = len(SUM_KEYS)
+        out = dict(zip(SUM_KEYS, vals[:n]))
+        out["valid"] = dict(zip(SUM_KEYS, vals[n:2 * n]))
+        counts = [int(x) for x in vals[2 * n:]]
+        out["steps"], out["contributed"], out["updates"] = counts[0], counts[1], counts[4]
+        out["valid"]["steps"], out["valid"]["contributed"] = counts[2], counts[3]
+        if reset:
+            t.zero_()
+            v.zero_()
+        return out
