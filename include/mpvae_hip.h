@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MPV_ABI_VERSION 15 /* 4: device-memory Philox keys (mpv_noise_philox*_dev);
+#define MPV_ABI_VERSION 16 /* 4: device-memory Philox keys (mpv_noise_philox*_dev);
                               5: T rows padded to roundup(L, 4) floats;
                               6: mpv_linear (the VAE's Linear layers); mpv_bwd_args
                                  dR64 and kl;
@@ -58,7 +58,9 @@ extern "C" {
                                  indiv_prob alone from a lean forward)
                              15: mpv_group_rows (the sensitive groups of a batch in
                                  one launch), mpv_label_weights_batch (every
-                                 target table in one launch) */
+                                 target table in one launch)
+                             16: mpv_split_eval (the evaluation's soft F1 and
+                                 fair_mean_diff over a whole split) */
 
 enum mpv_status { MPV_OK = 0, MPV_EINVAL = 1, MPV_ELAUNCH = 2 };
 enum mpv_dtype { MPV_F32 = 0, MPV_F64 = 1 };
@@ -470,8 +472,8 @@ int mpv_adam_finish(const mpv_adam_finish_args* args, void* stream);
  * mpv_label_weights_batch), group_rows, fair_fwd, fair_bwd, metrics, curve_keys, curve_sort (the LDS chunk sort), curve_merge
  * (the merge passes), curve_pass, curve_agg, metric_sweep (every launch of
  * mpv_threshold_sweep), calib_fwd, calib_tables, calib_bwd, probit_predict,
- * predict_final (the two launches of mpv_probit_predict).  Query synchronises
- * the recorded events. */
+ * predict_final (the two launches of mpv_probit_predict), split_eval, split_final
+ * (the two launches of mpv_split_eval).  Query synchronises the recorded events. */
 int mpv_timing_enable(int on);
 int mpv_timing_reset(void);
 int mpv_timing_query(const char* kernel, int64_t* launches, double* total_ms);
@@ -661,6 +663,47 @@ int mpv_calib_fwd(const mpv_calib_args* args, void* workspace, size_t workspace_
  * arguments and workspace.  Needs a threshold; an empty group's entries are 0. */
 int mpv_calib_bwd(const mpv_calib_args* args, const double* gout, float* g_threshold, float* g_p,
                   void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- Evaluation over a whole split (fairsoft_evaluate.py:83-121; evalsplit.hip)
+ * The "soft" F1 of the raw probabilities and the evaluation's fair_mean_diff,
+ * from one (N, L) buffer of indiv_prob.  fp64 arithmetic from fp32 inputs:
+ *   tp[l] = sum_i y p,  fp[l] = sum_i [y == 0] p,  fn[l] = sum_i y [p == 0]
+ *                                                            (evals.py:61-67)
+ *   miF1  = 2 sum tp / (2 sum tp + sum fp + sum fn)          (evals.py:99-100)
+ *   maF1  = mean over the labels where it is finite of
+ *           2 tp / (2 tp + fp + fn + 1e-6); NaN when there is none  (:104-109)
+ *   terms[t, k] = sum_l (m_tk[l] - m_t[l])^2 for a target t with W_t > 0 and a
+ *           group k with W_tk > 0, NaN otherwise; m_tk = sum_{i in k} w p / W_tk,
+ *           m_t = sum_i w p / W_t, W_t = sum_k W_tk  (fairsoft_evaluate.py:106-119)
+ *   out   = miF1, maF1, the mean of sqrt(terms) over the active terms (the
+ *           evaluation's fair_mean_diff), the mean of the terms themselves
+ *           (fairsoft_train_postprocess.py:444), the number of active terms;
+ *           both means are NaN when it is 0.
+ * Rows are grouped as for mpv_calib_args; an `order` entry outside [0, N) is
+ * skipped.  A group's rows are cut into R slices, one workgroup per (label
+ * chunk, group, slice); its lanes are (row, label) pairs, several rows per wave
+ * when L <= 32, 64-label chunks above.  Every sum runs in an order fixed by
+ * (N, L, T, G, R, goff): no floating-point atomics, two calls give the same
+ * bits; different R agree to fp64 rounding. */
+typedef struct mpv_split_eval_args {
+  const float* pred;    /* (N, L) indiv_prob of the whole split */
+  const float* target;  /* (N, L) exact 0 / 1 */
+  const double* w;      /* (T, N) row weights (mpv_label_weights[_batch]); unused when T = 0 */
+  const int32_t* order; /* (N) row indices group by group, or NULL: 0 .. N-1 */
+  const int32_t* goff;  /* (G + 1) group offsets into order, or NULL with G = 1: one group */
+  int64_t N, L, T, G;   /* 0 < N < 2^31, 0 < L <= 4096, T >= 0, 1 <= G <= 65535 */
+  int64_t R;            /* row slices per group, 1 .. 65535 */
+  double* counts;       /* (3, L) out: tp, fp, fn */
+  double* terms;        /* (T, G) out: squared distance of an active (t, k), NaN otherwise;
+                           NULL when T = 0 */
+  double* out;          /* (5) out: miF1, maF1, mean of sqrt(terms), mean of terms, number of
+                           active terms */
+} mpv_split_eval_args;
+
+/* 0 for a bad shape. */
+size_t mpv_split_eval_workspace_bytes(int64_t N, int64_t L, int64_t T, int64_t G, int64_t R);
+int mpv_split_eval(const mpv_split_eval_args* args, void* workspace, size_t workspace_bytes,
+                   void* stream);
 
 #ifdef __cplusplus
 }

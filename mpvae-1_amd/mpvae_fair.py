@@ -57,9 +57,15 @@ Differences from the reference:
 The post-process method's consumer of ``indiv_prob``
 (fairsoft_train_postprocess.py: one decision threshold per label and sensitive
 group, learned on a frozen model) runs in csrc/calib.hip: ``calibration_loss``,
-``calibrate`` and ``fair_mean_diff`` at the end of this module, with their own
-list of differences.
+``calibrate`` and ``fair_mean_diff`` further down, with their own list of
+differences.
+
+The evaluation's scoring of a whole split (fairsoft_evaluate.evaluate_mpvae,
+:83-121: the "soft" F1 of the raw probabilities and the mean Euclidean
+distance between group and split means) runs in csrc/evalsplit.hip:
+``split_scores`` at the end of this module, again with its own list.
 """
+import collections
 import ctypes
 
 import numpy as np
@@ -720,3 +726,203 @@ def fair_mean_diff(cal_prob, labels, sensitive_feat, centroids, tables, slices=N
     R = calib_slices(B, L, G, q.device) if slices is None else int(slices)
     out, _, _ = _calib_fwd(q, None, None, w, order, goff, G, R, False, False)
     return torch.where(unmatched | (out[2] == 0), nan, out[1] / out[2])
+
+
+# ------------------------------------------------------ evaluation over a split
+# fairsoft_evaluate.evaluate_mpvae's scoring (:83-121) on the device
+# (csrc/evalsplit.hip): the "soft" micro / macro F1 of the raw probabilities
+# and the mean Euclidean distance between the group and split weighted means.
+# Differences from the reference, none of them numeric beyond rounding:
+# * fp64 sums of the fp32 probabilities, where evals.compute_tp_fp_fn sums in
+#   fp32 and rounds tp / fp / fn to fp32 once more;
+# * the groups are the dataset's centroids, not ``np.unique`` of the split's
+#   own sensitive rows: the same partition, since a centroid with no row in
+#   the split adds nothing;
+# * a row whose sensitive pattern is no centroid makes the fairness fields NaN;
+# * the row weights are looked up in ``weight_labels`` (default: the split's
+#   own labels).  The reference looks them up in
+#   ``data.labels[np.arange(len(subset_idx))]`` -- the dataset's FIRST N rows,
+#   whatever rows the split holds (fairsoft_evaluate.py:94, :100); the two
+#   agree only for a split that is those rows.  A caller who wants the
+#   reference's number passes ``weight_labels=data.labels[:N]``.
+
+SplitScores = collections.namedtuple(
+    "SplitScores", ["miF1", "maF1", "fair_mean_diff", "fair_mean_sq", "fair_terms", "counts",
+                    "gid"])
+
+EVAL_MIN_STEPS = 4     # row steps a slice should hold before a group is cut further
+EVAL_MAX_SLICES = 64
+
+
+def eval_lanes(L):
+    """Lanes along the labels in csrc/evalsplit.hip's grid (eval_lanes there)."""
+    return 64 if L > 32 else 1 << max(0, int(L) - 1).bit_length()
+
+
+def eval_slices(N, L, G, device):
+    """R, the row slices per group of csrc/evalsplit.hip's grid: enough
+    workgroups (label chunk x group x slice) for two per compute unit, while a
+    slice of an evenly filled group keeps EVAL_MIN_STEPS steps of the 256 /
+    lanes rows a workgroup reads at once.  Host knowledge only."""
+    cus = torch.cuda.get_device_properties(device).multi_processor_count
+    lp = eval_lanes(L)
+    blocks = ((L + lp - 1) // lp) * G
+    want = (2 * cus + blocks - 1) // blocks
+    return max(1, min(want, N // (G * EVAL_MIN_STEPS * (256 // lp)), EVAL_MAX_SLICES))
+
+
+def _table_weights_host(labels, tables):
+    """``label_weights`` on CPU tensors, in torch: (T, N) fp64.  A row that is
+    not exact 0 / 1 after truncation gets 0, as in label_weights_kernel."""
+    y = labels.detach().float().trunc()
+    N, L = y.shape
+    W = (L + 63) // 64
+    bad = ~((y == 0) | (y == 1)).all(1)
+    bits = torch.zeros((N, W * 64), dtype=torch.int64)
+    bits[:, :L] = (y == 1).to(torch.int64)
+    shifts = torch.arange(64, dtype=torch.int64)
+    words = (bits.reshape(N, W, 64) << shifts).sum(-1)  # distinct bits: the sum is the OR
+    w = torch.zeros((len(tables), N), dtype=torch.float64)
+    for t, tab in enumerate(tables):
+        if tab.L != L:
+            raise ValueError(f"table built for label_dim {tab.L}, labels have {L}")
+        if tab.nslots == 0:
+            continue
+        keys, vals, used = tab.keys.cpu(), tab.vals.cpu(), tab.used.cpu().bool()
+        for i0 in range(0, N, 1024):
+            hit = (words[i0:i0 + 1024, None, :] == keys[None]).all(-1) & used[None]  # (n, slots)
+            w[t, i0:i0 + 1024] = (hit.to(torch.float64) * vals[None]).sum(1)
+    w[:, bad] = 0.0
+    return w
+
+
+def _split_scores_host(p, y, w, gid, G):
+    """The formulas of mpv_split_eval in fp64 torch ops, for CPU tensors:
+    ``(counts (3, L), out (5,), terms (T, G) or None)``."""
+    p, y = p.double(), y.double()
+    counts = torch.stack([(y * p).sum(0), ((y == 0).double() * p).sum(0),
+                          (y * (p == 0).double()).sum(0)])
+    tp, fp, fn = counts
+    mi = 2 * tp.sum() / (2 * tp.sum() + fp.sum() + fn.sum())
+    f1 = 2 * tp / (2 * tp + fp + fn + 1e-6)
+    keep = torch.isfinite(f1)
+    ma = torch.where(keep, f1, torch.zeros_like(f1)).sum() / keep.sum()
+    nan = torch.full((), float("nan"), dtype=torch.float64)
+    if w is None:
+        return counts, torch.stack([mi, ma, nan, nan, torch.zeros((), dtype=torch.float64)]), None
+    onehot = (gid.long()[:, None] == torch.arange(G)[None]).double()  # (N, G)
+    Wtk = w @ onehot                                                 # (T, G)
+    S = torch.einsum("tn,ng,nl->tgl", w, onehot, p)
+    Wt = Wtk.sum(1)
+    m_t = S.sum(1) / Wt[:, None]
+    terms = ((S / Wtk[..., None] - m_t[:, None, :]) ** 2).sum(-1)
+    active = (Wt > 0)[:, None] & (Wtk > 0)
+    terms = torch.where(active, terms, nan)
+    n = active.sum().double()
+    zero = torch.zeros_like(terms)
+    dist = torch.where(active, terms.sqrt(), zero).sum() / n
+    sq = torch.where(active, terms, zero).sum() / n
+    return counts, torch.stack([mi, ma, dist, sq, n]), terms
+
+
+def _split_eval(p, y, w, order, goff, G, R):
+    """mpv_split_eval on contiguous device tensors -> (counts, out, terms)."""
+    N, L = p.shape
+    T = 0 if w is None else w.shape[0]
+    lib = H.load_library()
+    nbytes = lib.mpv_split_eval_workspace_bytes(N, L, T, G, R)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=p.device)
+    counts = torch.empty((3, L), dtype=torch.float64, device=p.device)
+    out = torch.empty(5, dtype=torch.float64, device=p.device)
+    terms = torch.empty((T, G), dtype=torch.float64, device=p.device) if T else None
+    a = H.SplitEvalArgs(H.ptr(p), H.ptr(y), H.ptr(w), H.ptr(order), H.ptr(goff), N, L, T, G, R,
+                        H.ptr(counts), H.ptr(terms), H.ptr(out))
+    H.check(lib.mpv_split_eval(ctypes.byref(a), H.ptr(ws), nbytes, H.stream_of(p.device)),
+            "mpv_split_eval")
+    return counts, out, terms
+
+
+def split_scores(pred, labels, sensitive_feat=None, centroids=None, tables=None,
+                 weight_labels=None, slices=None):
+    """The scoring of fairsoft_evaluate.evaluate_mpvae (:83-121) over a whole
+    split, from device tensors, with no host sync (capturable in a HIP graph).
+
+    pred           -- (N, L) indiv_prob of every row of the split
+    labels         -- (N, L) the split's labels, exact 0 / 1
+    sensitive_feat -- (N, n_sensitive) of the split's rows   } needed with
+    centroids      -- (G, n_sensitive) ``np.unique(data.sensitive_feat, axis=0)``  } ``tables``
+    tables         -- [LabelDistanceTable(label_distances[t], L, dev) for t in
+                      target_fair_labels]; None: the reference's
+                      ``eval_fairness=False`` (no grouping, the fairness fields
+                      None); ``[]``: no target, the fairness scalars NaN
+    weight_labels  -- (N, L) the labels the row weights are looked up by
+                      (default: ``labels``).  The reference reads
+                      ``data.labels[np.arange(len(subset_idx))]``, the dataset's
+                      first N rows and not the split's (:94, :100): pass those
+                      rows for the reference's number
+    slices         -- row slices per group of the kernel's grid (default:
+                      ``eval_slices``); the results agree to fp64 rounding
+    Returns a ``SplitScores``: ``miF1``, ``maF1`` (the "soft" F1 of the raw
+    probabilities, evals.py:61-109), ``fair_mean_diff`` (the mean over the
+    active (target, group) terms of the Euclidean distance between the group's
+    and the split's weighted mean of ``pred``, :106-121) and ``fair_mean_sq``
+    (the mean of the squared distances, what ``fair_mean_diff`` of this module
+    gives) as 0-d fp64 tensors on ``pred``'s device, ``fair_terms`` (T, G) the
+    squared distances (NaN where inactive), ``counts`` (3, L) tp / fp / fn and
+    ``gid`` (N,) the rows' group ids.  No active term gives NaN (the
+    reference's ``np.mean([])``), and so does a row that matches no centroid.
+    N = 0 returns NaN scores without a launch.
+
+    CUDA tensors run mpv_split_eval (csrc/evalsplit.hip).  CPU tensors run the
+    same formulas in fp64 torch ops (the reference evaluates small
+    configurations on the CPU; ``mpvae_step.EvalPass`` then runs the model
+    through libmpvae_host.so): dispatch by device, never a fallback."""
+    dev = pred.device
+    host = dev.type == "cpu"
+    fair = tables is not None
+    if fair and (sensitive_feat is None or centroids is None):
+        raise ValueError("split_scores with tables needs sensitive_feat and centroids")
+    used = (pred, labels) + ((sensitive_feat, centroids, weight_labels) if fair else ())
+    if host:
+        if any(t is not None and t.device.type != "cpu" for t in used):
+            raise RuntimeError("split_scores inputs must all live on one device")
+    else:
+        H.require_gpu(*used)
+    p = pred.detach().contiguous().float()
+    y = labels.detach().contiguous().float()
+    N, L = p.shape
+    if tuple(y.shape) != (N, L):
+        raise ValueError(f"labels {tuple(y.shape)} do not match pred {(N, L)}")
+    nan = torch.full((), float("nan"), dtype=torch.float64, device=dev)
+    T = len(tables) if fair else 0
+    G = centroids.shape[0] if fair else 1
+    if N == 0:  # shapes are host knowledge: no launch with an empty grid
+        return SplitScores(nan, nan.clone(), nan.clone() if fair else None,
+                           nan.clone() if fair else None,
+                           torch.full((T, G), float("nan"), dtype=torch.float64, device=dev)
+                           if fair else None,
+                           torch.zeros((3, L), dtype=torch.float64, device=dev),
+                           torch.zeros(0, dtype=torch.int32, device=dev) if fair else None)
+    gid = unmatched = order = goff = w = None
+    if fair:
+        gid, unmatched = centroid_ids(sensitive_feat, centroids)
+        wl = y if weight_labels is None else weight_labels.detach().contiguous().float()
+        if tuple(wl.shape) != (N, L):
+            raise ValueError(f"weight_labels {tuple(wl.shape)} do not match pred {(N, L)}")
+        if T:
+            w = _table_weights_host(wl, tables) if host else label_weights_batch(wl, tables)[0]
+    if host:
+        counts, out, terms = _split_scores_host(p, y, w, gid, G)
+    else:
+        if fair:
+            order, goff = _group_layout(gid, G)
+        R = eval_slices(N, L, G, dev) if slices is None else int(slices)
+        counts, out, terms = _split_eval(p, y, w, order, goff, G, R)
+    if not fair:
+        return SplitScores(out[0], out[1], None, None, None, counts, None)
+    if terms is None:
+        terms = torch.full((0, G), float("nan"), dtype=torch.float64, device=dev)
+    return SplitScores(out[0], out[1], torch.where(unmatched, nan, out[2]),
+                       torch.where(unmatched, nan, out[3]),
+                       torch.where(unmatched, torch.full_like(terms, float("nan")), terms),
+                       counts, gid)

@@ -13,7 +13,7 @@ import torch  # noqa: F401  (must precede the .so load: one HIP runtime per proc
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MPVAE_HIP_LIB", os.path.join(HERE, "libmpvae_hip.so"))
 
-ABI_VERSION = 15
+ABI_VERSION = 16
 F32, F64 = 0, 1
 G_TOTAL, G_NLL, G_NLL_X, G_C, G_C_X, G_KL = range(6)
 
@@ -172,6 +172,14 @@ class CalibArgs(ctypes.Structure):
                 ("cal_prob", vp), ("out", vp)]
 
 
+class SplitEvalArgs(ctypes.Structure):
+    """mpv_split_eval_args: the evaluation's soft F1 and fair_mean_diff (evalsplit.hip)."""
+    _fields_ = [("pred", vp), ("target", vp), ("w", vp), ("order", vp), ("goff", vp),
+                ("N", ctypes.c_int64), ("L", ctypes.c_int64), ("T", ctypes.c_int64),
+                ("G", ctypes.c_int64), ("R", ctypes.c_int64), ("counts", vp), ("terms", vp),
+                ("out", vp)]
+
+
 # name -> (restype, argtypes); exactly the symbols of include/mpvae_hip.h
 SIGNATURES = {
     "mpv_abi_version": (ctypes.c_int, []),
@@ -244,6 +252,8 @@ SIGNATURES = {
     "mpv_calib_fwd": (ctypes.c_int, [ctypes.POINTER(CalibArgs), vp, ctypes.c_size_t, vp]),
     "mpv_calib_bwd": (ctypes.c_int, [ctypes.POINTER(CalibArgs), vp, vp, vp, vp, ctypes.c_size_t,
                                      vp]),
+    "mpv_split_eval_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64] * 5),
+    "mpv_split_eval": (ctypes.c_int, [ctypes.POINTER(SplitEvalArgs), vp, ctypes.c_size_t, vp]),
 }
 
 _lib = None
@@ -308,7 +318,7 @@ KERNELS = ["noise_philox", "split", "probit_fwd", "fwd_combine", "finalize", "bw
            "kl_bwd", "label_weights", "group_rows", "fair_fwd", "fair_bwd", "metrics", "linear", "adam",
            "adam_finish", "curve_keys", "curve_sort", "curve_merge", "curve_pass", "curve_agg",
            "metric_sweep", "calib_fwd", "calib_tables", "calib_bwd", "probit_predict",
-           "predict_final"]
+           "predict_final", "split_eval", "split_final"]
 
 
 def kernel_times():

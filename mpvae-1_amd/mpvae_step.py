@@ -670,3 +670,145 @@ class FairTrainStep(TrainStep):
             t.zero_()
             v.zero_()
         return out
+
+
+EvalOut = collections.namedtuple("EvalOut", ["indiv_prob", "scores"])
+
+
+class EvalPass:
+    """fairsoft_evaluate.evaluate_mpvae's loop and scoring (:40-123) over one
+    split as one call, on the model's device: the model's ``indiv_prob`` of
+    every batch written into one preallocated (N, L) fp32 buffer (what
+    fairsoft_prediction_extract's extract_prediction_mpvae collects), then
+    ``mpvae_fair.split_scores`` on that buffer.
+
+    ``run(labels, feats, sensitive_feat=None, weight_labels=None)`` takes the
+    split's rows as tensors on the model's device and returns an ``EvalOut``:
+    ``indiv_prob`` (N, L) and ``scores`` (a ``mpvae_fair.SplitScores``, device
+    tensors).  ``read(out)`` is the only host sync: the reference's dict
+    ``{'fair_mean_diff', 'miF1', 'maF1'}`` as Python floats, ``fair_mean_diff``
+    None without ``tables`` (the reference's ``eval_fairness=False``).
+
+    The batches are the reference's, ``range(N // B + 1)`` over rows ``[i B,
+    min((i + 1) B, N))``; an empty last batch (N a multiple of B) is skipped:
+    it draws nothing and adds no row.  ``label_free=False`` (default): a batch
+    is ``model(label, feat)`` and ``mpvae.predict_proba(feat_out,
+    model.r_sqrt_sigma, args)`` -- the reference's RNG stream and the bits of
+    its ``compute_loss(...)[6]``: both encoders draw their reparameterisation
+    noise, and ``torch_cpu`` probit noise comes from the CPU generator.
+    ``label_free=True``: ``model.predict_proba(feat, args)``, the feature
+    branch alone (another, equally distributed noise stream).
+
+    ``args`` is read as ``predict_proba`` reads it (mode -> n_train_sample /
+    n_test_sample, z_dim, mpvae_noise, mpvae_seed, mpvae_gemm, mpvae_shard).
+    With a device-tensor ``args.mpvae_seed`` every batch advances the key
+    (``mpvae_seed_advance``, as TrainStep does), so every batch draws fresh
+    noise.  ``tables``, ``centroids``, ``weight_labels`` and ``slices`` are
+    those of ``split_scores`` -- see there for the reference's choice of the
+    rows its weights are looked up by.  The model is put in ``eval()`` mode
+    under ``no_grad`` and its previous mode is restored.
+
+    With Philox noise and a device seed nothing in ``run`` waits for the host,
+    and ``capture(labels, feats)`` records the full-batch body in one HIP
+    graph on static buffers: each full batch is then a copy in, a replay and a
+    device-to-device copy of the result into its rows; the ragged last batch
+    and the scoring run eagerly.  CPU tensors run the model through
+    libmpvae_host.so and the scoring in torch (``split_scores``)."""
+
+    def __init__(self, model, args, batch_size, tables=None, centroids=None, label_free=False,
+                 slices=None):
+        if int(batch_size) < 1:
+            raise ValueError(f"batch_size must be >= 1 (got {batch_size})")
+        if tables is not None and centroids is None:
+            raise ValueError("EvalPass with tables needs the dataset's centroids")
+        self.model, self.args, self.batch_size = model, args, int(batch_size)
+        self.tables = None if tables is None else list(tables)
+        self.centroids, self.label_free, self.slices = centroids, bool(label_free), slices
+        self.graph = None
+        self.label = self.feat = self.out = None
+
+    def _batch_args(self):
+        args = self.args
+        if isinstance(getattr(args, "mpvae_seed", None), torch.Tensor):
+            args = copy.copy(args)
+            args.mpvae_seed_advance = True
+        return args
+
+    def _batch(self, label, feat):
+        """indiv_prob (B, L) of one batch."""
+        import mpvae
+        args = self._batch_args()
+        if self.label_free:
+            return self.model.predict_proba(feat, args)
+        out = self.model(label, feat)
+        return mpvae.predict_proba(out[3], self.model.r_sqrt_sigma, args)
+
+    def run(self, labels, feats, sensitive_feat=None, weight_labels=None):
+        import mpvae_fair
+        if self.tables is not None and sensitive_feat is None:
+            raise ValueError("EvalPass with tables needs the split's sensitive_feat")
+        N, L = labels.shape
+        B = self.batch_size
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            with torch.no_grad():
+                buf = torch.empty((N, L), dtype=torch.float32, device=feats.device)
+                for i in range(N // B + 1):
+                    s, e = i * B, min((i + 1) * B, N)
+                    if e <= s:
+                        continue
+                    if self.graph is not None and e - s == B:
+                        self.label.copy_(labels[s:e])
+                        self.feat.copy_(feats[s:e])
+                        self.graph.replay()
+                        buf[s:e].copy_(self.out)
+                    else:
+                        buf[s:e].copy_(self._batch(labels[s:e].float(), feats[s:e]))
+                scores = mpvae_fair.split_scores(buf, labels, sensitive_feat, self.centroids,
+                                                 self.tables, weight_labels, self.slices)
+        finally:
+            self.model.train(was_training)
+        return EvalOut(buf, scores)
+
+    def capture(self, labels, feats, warmup=2):
+        """Record the body of a full batch in a HIP graph on static copies of the
+        first ``batch_size`` rows of (labels, feats).  ``warmup`` eager batches
+        on a side stream first (they advance the device seed, as any batch
+        does).  Needs ``args.mpvae_noise = "philox"`` and a device-tensor
+        ``args.mpvae_seed``, TrainStep.capture's conditions: any other noise
+        source is drawn on the host."""
+        B = self.batch_size
+        if getattr(self.args, "mpvae_noise", "torch_cpu") != "philox" or not isinstance(
+                getattr(self.args, "mpvae_seed", None), torch.Tensor):
+            raise ValueError("capture() needs args.mpvae_noise = 'philox' and a one-element int64 "
+                             "device tensor as args.mpvae_seed")
+        if labels.shape[0] < B:
+            raise ValueError(f"capture() needs a full batch of {B} rows (got {labels.shape[0]})")
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            with torch.no_grad():
+                self.label, self.feat = labels[:B].float().clone(), feats[:B].clone()
+                side = torch.cuda.Stream()
+                side.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(side):
+                    for _ in range(max(1, warmup)):
+                        self._batch(self.label, self.feat)
+                torch.cuda.current_stream().wait_stream(side)
+                self.graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(self.graph):
+                    self.out = self._batch(self.label, self.feat)
+        finally:
+            self.model.train(was_training)
+        return self.graph
+
+    @staticmethod
+    def read(out):
+        """The reference's result dict as Python floats, with one host sync."""
+        s = out.scores
+        vals = step_scalars(miF1=s.miF1, maF1=s.maF1,
+                            **({} if s.fair_mean_diff is None
+                               else {"fair_mean_diff": s.fair_mean_diff}))
+        return {"fair_mean_diff": vals.get("fair_mean_diff"), "miF1": vals["miF1"],
+                "maF1": vals["maF1"]}
