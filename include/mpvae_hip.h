@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MPV_ABI_VERSION 16 /* 4: device-memory Philox keys (mpv_noise_philox*_dev);
+#define MPV_ABI_VERSION 17 /* 4: device-memory Philox keys (mpv_noise_philox*_dev);
                               5: T rows padded to roundup(L, 4) floats;
                               6: mpv_linear (the VAE's Linear layers); mpv_bwd_args
                                  dR64 and kl;
@@ -60,7 +60,11 @@ extern "C" {
                                  one launch), mpv_label_weights_batch (every
                                  target table in one launch)
                              16: mpv_split_eval (the evaluation's soft F1 and
-                                 fair_mean_diff over a whole split) */
+                                 fair_mean_diff over a whole split)
+                             17: mpv_label_sim_weights (row weights from a
+                                 closed-form label similarity, no table),
+                                 mpv_split_eval_defs (a split scored under D
+                                 weight definitions in one pass) */
 
 enum mpv_status { MPV_OK = 0, MPV_EINVAL = 1, MPV_ELAUNCH = 2 };
 enum mpv_dtype { MPV_F32 = 0, MPV_F64 = 1 };
@@ -469,11 +473,11 @@ int mpv_adam_finish(const mpv_adam_finish_args* args, void* stream);
  * Kernel names: noise_philox, probit_fwd, fwd_combine, finalize, bwd_coef,
  * bwd_elem, dR_gemm, sum_slabs, convert, bstat_combine, reparam_fwd,
  * reparam_bwd, kl_bwd, linear, adam, adam_finish, label_weights (mpv_label_weights and
- * mpv_label_weights_batch), group_rows, fair_fwd, fair_bwd, metrics, curve_keys, curve_sort (the LDS chunk sort), curve_merge
+ * mpv_label_weights_batch), label_sim (mpv_label_sim_weights), group_rows, fair_fwd, fair_bwd, metrics, curve_keys, curve_sort (the LDS chunk sort), curve_merge
  * (the merge passes), curve_pass, curve_agg, metric_sweep (every launch of
  * mpv_threshold_sweep), calib_fwd, calib_tables, calib_bwd, probit_predict,
  * predict_final (the two launches of mpv_probit_predict), split_eval, split_final
- * (the two launches of mpv_split_eval).  Query synchronises the recorded events. */
+ * (the two launches of mpv_split_eval and of mpv_split_eval_defs).  Query synchronises the recorded events. */
 int mpv_timing_enable(int on);
 int mpv_timing_reset(void);
 int mpv_timing_query(const char* kernel, int64_t* launches, double* total_ms);
@@ -511,6 +515,41 @@ int mpv_label_weights(const float* y, int64_t B, int64_t L, const mpv_label_tabl
 int mpv_label_weights_batch(const float* y, int64_t B, int64_t L, const mpv_label_table* tables,
                             int64_t T, double* w /* (T, B) */, int32_t* contributed,
                             void* stream);
+
+/* Row weights from a closed-form similarity between the row's label pattern
+ * and a target pattern: what label_distance_obs.py's builders store in
+ * label_distances[target][row string], without the dict.  With n_and, n_or and
+ * n_xor the popcounts of row & target, row | target and row ^ target:
+ *   MPV_SIM_INDICATION  sim = n_xor == 0 ? 1 : 0                      (:9-25)
+ *   MPV_SIM_CONSTANT    sim = 1                                       (:28-44)
+ *   MPV_SIM_JACCARD     sim = n_xor == 0 ? 1 : n_and / n_or           (:54-69)
+ *   MPV_SIM_HAMMING     sim = (L - n_xor) / L                         (:120-127)
+ * in fp64, and the weight is sim, or with has_gamma
+ *   min(max(exp(gamma * (sim - 1)), clip_lo), clip_hi)                (:106-108)
+ * A row with no binary key (mpv_label_weights) gets 0 under every definition.
+ * Unlike a table, which holds the dataset's patterns only and gives 0 for any
+ * other, every binary row gets its formula weight. */
+enum mpv_sim_kind {
+  MPV_SIM_INDICATION = 0,
+  MPV_SIM_CONSTANT = 1,
+  MPV_SIM_JACCARD = 2,
+  MPV_SIM_HAMMING = 3
+};
+typedef struct mpv_label_sim {
+  const uint64_t* target; /* W = ceil(L / 64) words in device memory, packed as a table's keys */
+  int32_t kind;           /* mpv_sim_kind */
+  int32_t has_gamma;
+  double gamma, clip_lo, clip_hi; /* read with has_gamma only */
+} mpv_label_sim;
+
+/* w (T, B): row t the weights under sims[t] (a host array of T structs);
+ * *contributed grows by the number of positive weights.  The definitions go to
+ * the kernel by value, MPV_LABEL_SIMS_PER_LAUNCH per launch; a row is packed
+ * once per launch.  Supported: 1 <= L <= 4096, B, T >= 1, every kind valid and
+ * every target non-NULL; anything else is MPV_EINVAL and launches nothing. */
+#define MPV_LABEL_SIMS_PER_LAUNCH 8
+int mpv_label_sim_weights(const float* y, int64_t B, int64_t L, const mpv_label_sim* sims,
+                          int64_t T, double* w /* (T, B) */, int32_t* contributed, void* stream);
 
 /* The sensitive groups of a batch (fairsoft_train.py:81 torch.unique(x, dim=0)
  * and the row masks of :106-111) in one launch of one workgroup.  x is (B, n)
@@ -704,6 +743,18 @@ typedef struct mpv_split_eval_args {
 size_t mpv_split_eval_workspace_bytes(int64_t N, int64_t L, int64_t T, int64_t G, int64_t R);
 int mpv_split_eval(const mpv_split_eval_args* args, void* workspace, size_t workspace_bytes,
                    void* stream);
+
+/* mpv_split_eval under D definitions of the row weights from one pass over the
+ * split (fairsoft_metric.evaluate_models_over_label_distances scores one set of
+ * predictions under every distance definition): args->T is the number of
+ * targets per definition, args->w is (D, T, N), args->terms (D, T, G), and
+ * out_defs (D, 3) holds per definition the mean of sqrt(terms), the mean of the
+ * terms and the number of active terms -- the bits mpv_split_eval gives for
+ * that definition alone (same N, L, G, R, goff).  args->out[0..1] are miF1 and
+ * maF1, args->out[2..4] repeat definition 0.  The workspace is
+ * mpv_split_eval_workspace_bytes(N, L, D * T, G, R); 1 <= D, D * T <= 2^20. */
+int mpv_split_eval_defs(const mpv_split_eval_args* args, int64_t D, double* out_defs,
+                        void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

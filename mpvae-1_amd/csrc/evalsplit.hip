@@ -12,6 +12,11 @@
 //                       (:106-121) and of their squares
 //                       (fairsoft_train_postprocess.py:444).
 //
+// mpv_split_eval_defs scores the same buffer under D definitions of the row
+// weights (the distance sweep of fairsoft_metric.py): split_eval sees D * T
+// targets, split_final takes the two means per definition, each as the call
+// on that definition alone takes them; mpv_split_eval is D = 1.
+//
 // Grid of split_eval: (label chunk) x (group k) x (row slice r of R).  A
 // workgroup's 256 lanes are (row, label) pairs: `lp` lanes along the labels
 // (the power of two >= L when L <= 32, else one 64-label chunk: a 256-B row
@@ -178,8 +183,17 @@ MPV_DEV double eval_sum(double v, double* red) {
 
 // One block.  The workspace's tables are written and read back by this block
 // alone, with a barrier between the phases.
+//
+// `a.T` targets are D definitions of a.T / D targets each: everything up to
+// terms[] is per target, and the means over a definition's (target, group)
+// pairs walk them as a call on that definition alone would (thread tid takes
+// pairs tid, tid + 256, ... of the definition, then the block sum), so each
+// definition's three numbers carry the bits of its own call.  out_defs NULL
+// (D = 1): they go to a.out[2..4]; else to out_defs[d * 3 ..], and a.out[2..4]
+// hold definition 0's.
 __global__ __launch_bounds__(kEvalThreads) void split_final_kernel(mpv_split_eval_args a,
-                                                                   EvalWs ws) {
+                                                                   EvalWs ws, int D,
+                                                                   double* __restrict__ out_defs) {
   __shared__ double red[kEvalWaves];
   const int64_t L = a.L, T = a.T, G = a.G, R = a.R;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -240,18 +254,32 @@ __global__ __launch_bounds__(kEvalThreads) void split_final_kernel(mpv_split_eva
     if (lane == 0) a.terms[i] = (Wt > 0.0 && Wk > 0.0) ? s : nan;
   }
   __syncthreads();
-  double dist = 0.0, sq = 0.0, cnt = 0.0;
-  for (int64_t i = tid; i < T * G; i += kEvalThreads) {
-    const double v = a.terms[i];
-    if (v == v) {
-      dist += sqrt(v);  // :118-119
-      sq += v;
-      cnt += 1.0;
+  const int64_t per = T / D * G;  // (target, group) pairs of one definition
+  for (int d = 0; d < D; ++d) {
+    double dist = 0.0, sq = 0.0, cnt = 0.0;
+    for (int64_t i = tid; i < per; i += kEvalThreads) {
+      const double v = a.terms[d * per + i];
+      if (v == v) {
+        dist += sqrt(v);  // :118-119
+        sq += v;
+        cnt += 1.0;
+      }
+    }
+    dist = eval_sum(dist, red);
+    sq = eval_sum(sq, red);
+    cnt = eval_sum(cnt, red);
+    if (tid == 0) {
+      double* o = out_defs != nullptr ? out_defs + 3 * d : a.out + 2;
+      o[0] = dist / cnt;  // np.mean([]) is NaN
+      o[1] = sq / cnt;
+      o[2] = cnt;
+      if (out_defs != nullptr && d == 0) {
+        a.out[2] = o[0];
+        a.out[3] = o[1];
+        a.out[4] = o[2];
+      }
     }
   }
-  dist = eval_sum(dist, red);
-  sq = eval_sum(sq, red);
-  cnt = eval_sum(cnt, red);
   double tp = 0.0, fp = 0.0, fn = 0.0, f1 = 0.0, nf = 0.0;
   for (int64_t l = tid; l < L; l += kEvalThreads) {
     const double t = a.counts[l], p = a.counts[L + l], n = a.counts[2 * L + l];
@@ -272,15 +300,45 @@ __global__ __launch_bounds__(kEvalThreads) void split_final_kernel(mpv_split_eva
   if (tid == 0) {
     a.out[0] = 2.0 * tp / (2.0 * tp + fp + fn);  // evals.py:99-100
     a.out[1] = f1 / nf;                          // np.mean of the kept labels; none: NaN
-    a.out[2] = dist / cnt;                       // np.mean([]) is NaN
-    a.out[3] = sq / cnt;
-    a.out[4] = cnt;
   }
 }
 
 }  // namespace mpv
 
 using namespace mpv;
+
+// mpv_split_eval (D = 1, out_defs NULL) and mpv_split_eval_defs: `a->T` targets
+// in each of D definitions, laid out as D * a->T targets.
+static int split_eval_run(const mpv_split_eval_args* a, int64_t D, double* out_defs,
+                          void* workspace, size_t workspace_bytes, void* stream) {
+  MPV_REQUIRE(a != nullptr, "mpv_split_eval_args is NULL");
+  MPV_REQUIRE(D >= 1 && D <= (int64_t(1) << 20), "definitions D must be in 1 .. 2^20 (got %lld)",
+              (long long)D);
+  MPV_REQUIRE(a->N > 0 && a->N < (int64_t(1) << 31) && a->L > 0 && a->L <= 4096 && a->T >= 0 &&
+                  a->T * D <= (int64_t(1) << 20) && a->G >= 1 && a->G <= 65535,
+              "bad split shape N=%lld L=%lld T=%lld G=%lld", (long long)a->N, (long long)a->L,
+              (long long)(a->T * D), (long long)a->G);
+  MPV_REQUIRE(a->R >= 1 && a->R <= 65535, "split row slices R must be in 1 .. 65535 (got %lld)",
+              (long long)a->R);
+  MPV_REQUIRE(a->pred && a->target, "NULL pred / target in mpv_split_eval_args");
+  MPV_REQUIRE(a->goff != nullptr || a->G == 1, "NULL goff with G = %lld groups", (long long)a->G);
+  MPV_REQUIRE(a->T == 0 || (a->w != nullptr && a->terms != nullptr), "NULL w / terms with T > 0");
+  MPV_REQUIRE(a->counts && a->out, "NULL counts / out in mpv_split_eval_args");
+  mpv_split_eval_args all = *a;
+  all.T = a->T * D;
+  const size_t need = mpv_split_eval_workspace_bytes(all.N, all.L, all.T, all.G, all.R);
+  MPV_REQUIRE(workspace && need && workspace_bytes >= need, "split workspace too small");
+  hipStream_t st = as_stream(stream);
+  const EvalWs ws = eval_ws(workspace, all.L, all.T, all.G, all.R);
+  const int lp = eval_lanes(all.L);
+  MPV_LAUNCH("split_eval", split_eval_kernel,
+             dim3((unsigned)cdiv(all.L, lp), (unsigned)all.G, (unsigned)all.R), dim3(kEvalThreads),
+             0, st, all, ws, lp);
+  if (int rc = check_launch("split_eval")) return rc;
+  MPV_LAUNCH("split_final", split_final_kernel, dim3(1), dim3(kEvalThreads), 0, st, all, ws,
+             (int)D, out_defs);
+  return check_launch("split_final");
+}
 
 extern "C" {
 
@@ -294,28 +352,13 @@ size_t mpv_split_eval_workspace_bytes(int64_t N, int64_t L, int64_t T, int64_t G
 
 int mpv_split_eval(const mpv_split_eval_args* a, void* workspace, size_t workspace_bytes,
                    void* stream) {
-  MPV_REQUIRE(a != nullptr, "mpv_split_eval_args is NULL");
-  MPV_REQUIRE(a->N > 0 && a->N < (int64_t(1) << 31) && a->L > 0 && a->L <= 4096 && a->T >= 0 &&
-                  a->T <= (int64_t(1) << 20) && a->G >= 1 && a->G <= 65535,
-              "bad split shape N=%lld L=%lld T=%lld G=%lld", (long long)a->N, (long long)a->L,
-              (long long)a->T, (long long)a->G);
-  MPV_REQUIRE(a->R >= 1 && a->R <= 65535, "split row slices R must be in 1 .. 65535 (got %lld)",
-              (long long)a->R);
-  MPV_REQUIRE(a->pred && a->target, "NULL pred / target in mpv_split_eval_args");
-  MPV_REQUIRE(a->goff != nullptr || a->G == 1, "NULL goff with G = %lld groups", (long long)a->G);
-  MPV_REQUIRE(a->T == 0 || (a->w != nullptr && a->terms != nullptr), "NULL w / terms with T > 0");
-  MPV_REQUIRE(a->counts && a->out, "NULL counts / out in mpv_split_eval_args");
-  const size_t need = mpv_split_eval_workspace_bytes(a->N, a->L, a->T, a->G, a->R);
-  MPV_REQUIRE(workspace && need && workspace_bytes >= need, "split workspace too small");
-  hipStream_t st = as_stream(stream);
-  const EvalWs ws = eval_ws(workspace, a->L, a->T, a->G, a->R);
-  const int lp = eval_lanes(a->L);
-  MPV_LAUNCH("split_eval", split_eval_kernel,
-             dim3((unsigned)cdiv(a->L, lp), (unsigned)a->G, (unsigned)a->R), dim3(kEvalThreads), 0,
-             st, *a, ws, lp);
-  if (int rc = check_launch("split_eval")) return rc;
-  MPV_LAUNCH("split_final", split_final_kernel, dim3(1), dim3(kEvalThreads), 0, st, *a, ws);
-  return check_launch("split_final");
+  return split_eval_run(a, 1, nullptr, workspace, workspace_bytes, stream);
+}
+
+int mpv_split_eval_defs(const mpv_split_eval_args* a, int64_t D, double* out_defs,
+                        void* workspace, size_t workspace_bytes, void* stream) {
+  MPV_REQUIRE(out_defs != nullptr, "NULL out_defs in mpv_split_eval_defs");
+  return split_eval_run(a, D, out_defs, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -10,6 +10,12 @@
 //                          and dict lookup per row.
 //   label_weights_batch_   the same for up to MPV_LABEL_TABLES_PER_LAUNCH target
 //   kernel                 tables in one launch: the row packed and hashed once.
+//   label_sim_kernel       the weights without a dict: indication, constant,
+//                          Jaccard and Hamming similarity to a packed target
+//                          (label_distance_obs.py:9-168, with dist_gamma the
+//                          clipped exponential) from popcounts of the packed
+//                          row, up to MPV_LABEL_SIMS_PER_LAUNCH definitions a
+//                          launch.
 //   group_rows_kernel      the batch's sensitive groups (torch.unique(x, dim=0)'s
 //                          inverse, fairsoft_train.py:81, :106-111) with the
 //                          stable order by group and the group offsets, in one
@@ -121,6 +127,55 @@ __global__ __launch_bounds__(64 * kLwWaves) void label_weights_batch_kernel(
   int positive = 0;
   for (int t = 0; t < tabs.n; ++t) {
     const double val = bad ? 0.0 : probe_table(tabs.t[t], h, words[wv]);
+    if (lane == 0) w[(int64_t)t * B + b] = val;
+    positive += val > 0.0;
+  }
+  if (lane == 0 && positive) atomicAdd(contributed, positive);  // integer count: order-free
+}
+
+// Up to MPV_LABEL_SIMS_PER_LAUNCH similarity definitions by value: the weight
+// is a closed form of the row's and the target's bit patterns (what the
+// builders of label_distance_obs.py store per pair of label strings), so the
+// row is packed once and every definition costs three popcounts per word.
+struct LabelSims {
+  mpv_label_sim s[MPV_LABEL_SIMS_PER_LAUNCH];
+  int n;
+};
+
+__global__ __launch_bounds__(64 * kLwWaves) void label_sim_kernel(
+    const float* __restrict__ y, int B, int L, int W, LabelSims sims, double* __restrict__ w,
+    int* __restrict__ contributed) {
+  __shared__ uint64_t words[kLwWaves][64];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int b = blockIdx.x * kLwWaves + wv;
+  if (b >= B) return;
+  uint64_t h;
+  const bool bad = pack_row(y, b, L, W, words[wv], h);
+  const uint64_t row = lane < W ? words[wv][lane] : 0;
+  int positive = 0;
+  for (int t = 0; t < sims.n; ++t) {
+    const mpv_label_sim& s = sims.s[t];
+    const uint64_t tgt = lane < W ? s.target[lane] : 0;
+    int n_and = __popcll(row & tgt), n_or = __popcll(row | tgt), n_xor = __popcll(row ^ tgt);
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {  // integer sums: order-free
+      n_and += __shfl_xor(n_and, o, 64);
+      n_or += __shfl_xor(n_or, o, 64);
+      n_xor += __shfl_xor(n_xor, o, 64);
+    }
+    double sim = 1.0;  // MPV_SIM_CONSTANT
+    if (s.kind == MPV_SIM_INDICATION) {
+      sim = n_xor == 0 ? 1.0 : 0.0;
+    } else if (s.kind == MPV_SIM_JACCARD) {  // unequal patterns have n_or > 0
+      sim = n_xor == 0 ? 1.0 : (double)n_and / (double)n_or;
+    } else if (s.kind == MPV_SIM_HAMMING) {
+      sim = (double)(L - n_xor) / (double)L;
+    }
+    double val = sim;
+    // np.clip(np.exp(gamma * (sim - 1)), lo, hi): subtract, then multiply, so
+    // nothing is contracted and exp sees numpy's argument
+    if (s.has_gamma) val = fmin(fmax(exp(s.gamma * (sim - 1.0)), s.clip_lo), s.clip_hi);
+    if (bad) val = 0.0;
     if (lane == 0) w[(int64_t)t * B + b] = val;
     positive += val > 0.0;
   }
@@ -510,6 +565,28 @@ int mpv_label_weights_batch(const float* y, int64_t B, int64_t L, const mpv_labe
     MPV_LAUNCH("label_weights", label_weights_batch_kernel, dim3(blocks), dim3(64 * kLwWaves), 0,
                as_stream(stream), y, (int)B, (int)L, tabs, w + t0 * B, contributed);
     if (int rc = check_launch("label_weights_batch")) return rc;
+  }
+  return MPV_OK;
+}
+
+int mpv_label_sim_weights(const float* y, int64_t B, int64_t L, const mpv_label_sim* sims,
+                          int64_t T, double* w, int32_t* contributed, void* stream) {
+  MPV_REQUIRE(L >= 1 && L <= 4096, "label_sim_weights supports 1 <= label_dim <= 4096 (got %lld)",
+              (long long)L);
+  MPV_REQUIRE(y && sims && w && contributed && B > 0 && T > 0, "bad label_sim_weights arguments");
+  for (int64_t t = 0; t < T; ++t) {  // every definition is checked before the first launch
+    MPV_REQUIRE(sims[t].target != nullptr, "similarity %lld has no target", (long long)t);
+    MPV_REQUIRE(sims[t].kind >= MPV_SIM_INDICATION && sims[t].kind <= MPV_SIM_HAMMING,
+                "similarity %lld: unknown kind %d", (long long)t, (int)sims[t].kind);
+  }
+  const int blocks = (int)cdiv(B, kLwWaves), W = (int)cdiv(L, 64);
+  for (int64_t t0 = 0; t0 < T; t0 += MPV_LABEL_SIMS_PER_LAUNCH) {
+    LabelSims chunk;
+    chunk.n = (int)(T - t0 < MPV_LABEL_SIMS_PER_LAUNCH ? T - t0 : MPV_LABEL_SIMS_PER_LAUNCH);
+    for (int i = 0; i < MPV_LABEL_SIMS_PER_LAUNCH; ++i) chunk.s[i] = sims[t0 + (i < chunk.n ? i : 0)];
+    MPV_LAUNCH("label_sim", label_sim_kernel, dim3(blocks), dim3(64 * kLwWaves), 0,
+               as_stream(stream), y, (int)B, (int)L, W, chunk, w + t0 * B, contributed);
+    if (int rc = check_launch("label_sim")) return rc;
   }
   return MPV_OK;
 }

@@ -29,6 +29,13 @@ Differences from the reference, none of them numeric:
   reference's dtype (fp32 when every table holds Python floats), its value
   differs from the reference's fp32 one by fp32 rounding only
   (tests/golden fair_f6/f7, tests/test_gpu_fair.py);
+* a ``LabelSimilarity`` (the row weights as a closed form of the row's and
+  the target's patterns, label_sim_kernel; accepted wherever a
+  ``LabelDistanceTable`` is) gives every binary row its formula weight, where
+  the reference's dict holds only the patterns that occur in the dataset and
+  ``.get(key, 0.)`` gives 0 for any other.  The two agree for rows taken from
+  the dataset, which the train, validation and test splits always are; a
+  caller who needs the miss keeps the table;
 * the metrics come back as 0-d fp64 device tensors (``.item()`` works as on
   the reference's numpy scalars); p@k ties go to the larger label index
   (numpy's default argsort is not stable, so the reference's tie order is
@@ -63,7 +70,10 @@ differences.
 The evaluation's scoring of a whole split (fairsoft_evaluate.evaluate_mpvae,
 :83-121: the "soft" F1 of the raw probabilities and the mean Euclidean
 distance between group and split means) runs in csrc/evalsplit.hip:
-``split_scores`` at the end of this module, again with its own list.
+``split_scores`` at the end of this module, again with its own list, and
+``split_scores_defs``, the same split scored under many weight definitions
+(the distance sweep of fairsoft_metric.evaluate_models_over_label_distances)
+from one pass.
 """
 import collections
 import ctypes
@@ -150,9 +160,152 @@ class LabelDistanceTable:
                             self.W)
 
 
+SIM_KINDS = {"indication": H.SIM_INDICATION, "constant": H.SIM_CONSTANT,
+             "jaccard": H.SIM_JACCARD, "hamming": H.SIM_HAMMING}
+
+
+class LabelSimilarity:
+    """One target label's row weights as a closed form of the row's and the
+    target's 0/1 patterns: what label_distance_obs.py's builders store in
+    ``label_distances[target]`` (indication_similarity :9-25,
+    constant_similarity :28-44, str_jac_similarity :54-69, str_ham_similarity
+    :120-127; with ``gamma`` the ``np.clip(np.exp(gamma * (sim - 1)), *clip)``
+    of the ``_nonlinear`` builders, :106-108), computed per row on the device
+    (label_sim_kernel) instead of built as a dict over every pair of the
+    dataset's patterns.  Accepted wherever a ``LabelDistanceTable`` is, also
+    mixed with tables in one list.
+
+    kind      -- "indication", "constant", "jaccard" or "hamming"
+    target    -- the target pattern: a 0/1 vector of length ``label_dim`` or
+                 the reference's key string
+    gamma     -- the reference's ``args.dist_gamma``; None: the similarity itself
+    clip      -- (minimum_clip, maximum_clip), read with ``gamma`` only
+
+    ``ref_dtype`` follows ``LabelDistanceTable``'s rule: with a gamma the
+    reference stores numpy float64 values (fp64), without it Python floats
+    (fp32).  ``kind="hamming"`` without gamma is ``str_ham_similarity``; the
+    reference's own wrapper for that case (``_hamming_similarity``) raises.
+
+    The one difference from the reference's dict: the dict holds the
+    dataset's patterns only and gives 0 for any other row, the closed form
+    gives every binary row its formula weight.  Rows taken from the dataset
+    (the train, validation and test splits) get the same weight either way; a
+    caller who needs the miss keeps the table."""
+
+    def __init__(self, kind, target, label_dim, device, gamma=None, clip=(0.0, 1.0)):
+        if kind not in SIM_KINDS:
+            raise ValueError(f"unknown similarity kind {kind!r} (one of {sorted(SIM_KINDS)})")
+        self.kind, self.L, self.W = kind, int(label_dim), (int(label_dim) + 63) // 64
+        if not isinstance(target, str):
+            vals = torch.as_tensor(target).reshape(-1).tolist()
+            if any(v not in (0, 1) for v in vals):
+                raise ValueError("a similarity target must be a 0/1 pattern")
+            target = "".join(str(int(v)) for v in vals)
+        words = pack_pattern(target, self.L)
+        if words is None:
+            raise ValueError(f"target {target!r} is not a 0/1 pattern of length {self.L}")
+        self.key = target
+        self.gamma = None if gamma is None else float(gamma)
+        self.clip = (float(clip[0]), float(clip[1]))
+        self.ref_dtype = torch.float32 if gamma is None else torch.float64
+        self.target = torch.from_numpy(np.array(words, np.uint64).view(np.int64).copy()).to(device)
+
+    def c_struct(self):
+        return H.LabelSim(H.ptr(self.target), SIM_KINDS[self.kind], int(self.gamma is not None),
+                          0.0 if self.gamma is None else self.gamma, self.clip[0], self.clip[1])
+
+
+def _check_label_dim(sources, L):
+    for s in sources:
+        if s.L != L:
+            what = "similarity" if isinstance(s, LabelSimilarity) else "table"
+            raise ValueError(f"{what} built for label_dim {s.L}, labels have {L}")
+
+
+def _source_runs(sources):
+    """The maximal runs of one kind in a list of weight sources:
+    ``[(t0, t1, is_similarity)]``; each run fills rows [t0, t1) of w."""
+    runs = []
+    for t, s in enumerate(sources):
+        sim = isinstance(s, LabelSimilarity)
+        if runs and runs[-1][2] == sim:
+            runs[-1][1] = t + 1
+        else:
+            runs.append([t, t + 1, sim])
+    return runs
+
+
+def _sim_weights_into(y, sims, w, count):
+    """mpv_label_sim_weights on contiguous fp32 device labels into rows of w."""
+    B, L = y.shape
+    structs = (H.LabelSim * max(1, len(sims)))(*[s.c_struct() for s in sims])
+    H.check(H.load_library().mpv_label_sim_weights(H.ptr(y), B, L, structs, len(sims), H.ptr(w),
+                                                   H.ptr(count), H.stream_of(y.device)),
+            "mpv_label_sim_weights")
+
+
+def _sim_weights_host(labels, sims):
+    """``similarity_weights`` on CPU tensors: label_sim_kernel's formulas in
+    fp64 torch ops, (T, N).  A row that is not exact 0 / 1 after truncation
+    gets 0."""
+    y = labels.detach().float().trunc()
+    N, L = y.shape
+    bad = ~((y == 0) | (y == 1)).all(1)
+    bits = y == 1
+    w = torch.zeros((len(sims), N), dtype=torch.float64)
+    one = torch.ones(N, dtype=torch.float64)
+    for t, s in enumerate(sims):
+        tgt = torch.tensor([c == "1" for c in s.key], dtype=torch.bool)
+        n_and = (bits & tgt).sum(1).double()
+        n_or = (bits | tgt).sum(1).double()
+        n_xor = (bits ^ tgt).sum(1).double()
+        if s.kind == "indication":
+            sim = (n_xor == 0).double()
+        elif s.kind == "constant":
+            sim = one
+        elif s.kind == "jaccard":
+            sim = torch.where(n_xor == 0, one, n_and / n_or.clamp(min=1.0))
+        else:
+            sim = (L - n_xor) / L
+        if s.gamma is not None:
+            sim = torch.exp(s.gamma * (sim - 1.0)).clamp(s.clip[0], s.clip[1])
+        w[t] = sim
+    w[:, bad] = 0.0
+    return w
+
+
+def similarity_weights(labels, sims):
+    """``(w (T, B) fp64, count int32)``: row t the weights of ``labels``' rows
+    under the ``LabelSimilarity`` ``sims[t]``, and the number of positive
+    weights (the reference's contributed_reg_fair_sample, fairsoft_train.py:
+    91-92).  A row whose ``int()`` values are not all 0 or 1 gets 0 under every
+    definition.  CUDA tensors run mpv_label_sim_weights (one launch per
+    ``H.LABEL_SIMS_PER_LAUNCH`` definitions, no host sync); CPU tensors run the
+    same formulas in fp64 torch ops: dispatch by device, never a fallback."""
+    sims = list(sims)
+    if any(not isinstance(s, LabelSimilarity) for s in sims):
+        raise TypeError("similarity_weights takes LabelSimilarity objects")
+    L = labels.shape[1]
+    _check_label_dim(sims, L)
+    if labels.device.type == "cpu":
+        w = _sim_weights_host(labels, sims)
+        return w, (w > 0).sum().to(torch.int32)
+    H.require_gpu(labels)
+    y = labels.contiguous().float()
+    B = y.shape[0]
+    w = torch.empty((len(sims), B), dtype=torch.float64, device=y.device)
+    count = torch.zeros((), dtype=torch.int32, device=y.device)
+    if B == 0:  # no row to weigh: no launch with an empty grid
+        return w, count
+    _sim_weights_into(y, sims, w, count)
+    return w, count
+
+
 def label_weights(labels, tables):
     """(T, B) fp64 row weights, one row per target table, and the int32 count
-    of (target, row) pairs with a positive weight (fairsoft_train.py:85-93)."""
+    of (target, row) pairs with a positive weight (fairsoft_train.py:85-93).
+    A ``LabelSimilarity`` in the list fills its row from its closed form
+    (mpv_label_sim_weights), one launch each."""
     H.require_gpu(labels)
     y = labels.contiguous().float()
     B, L = y.shape
@@ -161,9 +314,11 @@ def label_weights(labels, tables):
     if B == 0:  # no row to look up: no launch with an empty grid
         return w, count
     lib, st = H.load_library(), H.stream_of(y.device)
+    _check_label_dim(tables, L)
     for t, tab in enumerate(tables):
-        if tab.L != L:
-            raise ValueError(f"table built for label_dim {tab.L}, labels have {L}")
+        if isinstance(tab, LabelSimilarity):
+            _sim_weights_into(y, [tab], w[t], count)
+            continue
         s = tab.c_struct()
         H.check(lib.mpv_label_weights(H.ptr(y), B, L, ctypes.byref(s), H.ptr(w[t]), H.ptr(count),
                                       st), "mpv_label_weights")
@@ -174,7 +329,9 @@ def label_weights_batch(labels, tables):
     """``label_weights`` with every target table in one launch per
     ``H.LABEL_TABLES_PER_LAUNCH`` tables (mpv_label_weights_batch): each row is
     packed and hashed once, then looked up in every table.  The same ``(w,
-    count)``, bit for bit."""
+    count)``, bit for bit.  A list may mix tables and ``LabelSimilarity``
+    objects: every maximal run of one kind is one call (mpv_label_weights_batch
+    or mpv_label_sim_weights) that fills the run's rows of w."""
     H.require_gpu(labels)
     y = labels.contiguous().float()
     B, L = y.shape
@@ -182,13 +339,16 @@ def label_weights_batch(labels, tables):
     count = torch.zeros((), dtype=torch.int32, device=y.device)
     if B == 0 or not tables:  # nothing to look up: no launch with an empty grid
         return w, count
-    for tab in tables:
-        if tab.L != L:
-            raise ValueError(f"table built for label_dim {tab.L}, labels have {L}")
-    structs = (H.LabelTable * len(tables))(*[tab.c_struct() for tab in tables])
-    H.check(H.load_library().mpv_label_weights_batch(H.ptr(y), B, L, structs, len(tables), H.ptr(w),
-                                                     H.ptr(count), H.stream_of(y.device)),
-            "mpv_label_weights_batch")
+    _check_label_dim(tables, L)
+    for t0, t1, sim in _source_runs(tables):
+        if sim:
+            _sim_weights_into(y, tables[t0:t1], w[t0], count)
+            continue
+        structs = (H.LabelTable * (t1 - t0))(*[tab.c_struct() for tab in tables[t0:t1]])
+        H.check(H.load_library().mpv_label_weights_batch(H.ptr(y), B, L, structs, t1 - t0,
+                                                         H.ptr(w[t0]), H.ptr(count),
+                                                         H.stream_of(y.device)),
+                "mpv_label_weights_batch")
     return w, count
 
 
@@ -335,7 +495,8 @@ def fairness_penalty(indiv_prob_label, indiv_prob, input_label, sensitive_feat, 
     input_label                   -- (B, L) batch labels (data.labels[idx])
     sensitive_feat                -- (B, n_sensitive) (data.sensitive_feat[idx])
     tables                        -- [LabelDistanceTable(label_distances[t], L, dev)
-                                      for t in target_fair_labels]
+                                      for t in target_fair_labels], or
+                                     ``LabelSimilarity`` objects, or both mixed
     max_groups                    -- optional upper bound on the distinct sensitive
                                      patterns in a batch (default: the batch size;
                                      a batch with more distinct patterns than the
@@ -796,6 +957,16 @@ def _table_weights_host(labels, tables):
     return w
 
 
+def _weights_host(labels, sources):
+    """``label_weights_batch`` on CPU tensors for a list that may mix tables
+    and ``LabelSimilarity`` objects: (T, N) fp64."""
+    _check_label_dim(sources, labels.shape[1])
+    w = torch.zeros((len(sources), labels.shape[0]), dtype=torch.float64)
+    for t0, t1, sim in _source_runs(sources):
+        w[t0:t1] = (_sim_weights_host if sim else _table_weights_host)(labels, sources[t0:t1])
+    return w
+
+
 def _split_scores_host(p, y, w, gid, G):
     """The formulas of mpv_split_eval in fp64 torch ops, for CPU tensors:
     ``(counts (3, L), out (5,), terms (T, G) or None)``."""
@@ -910,7 +1081,7 @@ def split_scores(pred, labels, sensitive_feat=None, centroids=None, tables=None,
         if tuple(wl.shape) != (N, L):
             raise ValueError(f"weight_labels {tuple(wl.shape)} do not match pred {(N, L)}")
         if T:
-            w = _table_weights_host(wl, tables) if host else label_weights_batch(wl, tables)[0]
+            w = _weights_host(wl, tables) if host else label_weights_batch(wl, tables)[0]
     if host:
         counts, out, terms = _split_scores_host(p, y, w, gid, G)
     else:
@@ -924,5 +1095,94 @@ def split_scores(pred, labels, sensitive_feat=None, centroids=None, tables=None,
         terms = torch.full((0, G), float("nan"), dtype=torch.float64, device=dev)
     return SplitScores(out[0], out[1], torch.where(unmatched, nan, out[2]),
                        torch.where(unmatched, nan, out[3]),
+                       torch.where(unmatched, torch.full_like(terms, float("nan")), terms),
+                       counts, gid)
+
+
+def _split_eval_defs(p, y, w, order, goff, G, R, D, T):
+    """mpv_split_eval_defs on contiguous device tensors -> (counts, out (5,),
+    out_defs (D, 3), terms (D, T, G))."""
+    N, L = p.shape
+    lib = H.load_library()
+    nbytes = lib.mpv_split_eval_workspace_bytes(N, L, D * T, G, R)
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=p.device)
+    counts = torch.empty((3, L), dtype=torch.float64, device=p.device)
+    out = torch.empty(5, dtype=torch.float64, device=p.device)
+    out_defs = torch.empty((max(D, 1), 3), dtype=torch.float64, device=p.device)
+    terms = torch.empty((D, T, G), dtype=torch.float64, device=p.device)
+    a = H.SplitEvalArgs(H.ptr(p), H.ptr(y), H.ptr(w), H.ptr(order), H.ptr(goff), N, L, T, G, R,
+                        H.ptr(counts), H.ptr(terms) if D * T else None, H.ptr(out))
+    H.check(lib.mpv_split_eval_defs(ctypes.byref(a), D, H.ptr(out_defs), H.ptr(ws), nbytes,
+                                    H.stream_of(p.device)), "mpv_split_eval_defs")
+    return counts, out, out_defs, terms
+
+
+def split_scores_defs(pred, labels, sensitive_feat, centroids, definitions, weight_labels=None,
+                      slices=None):
+    """``split_scores`` under D definitions of the row weights from one pass
+    over the split: what fairsoft_metric.evaluate_models_over_label_distances
+    gets from one full ``evaluate_mpvae`` per distance definition, although
+    ``indiv_prob`` does not depend on the definition.
+
+    definitions -- a list of D lists of T weight sources each (``LabelSimilarity``
+                   or ``LabelDistanceTable``, as ``split_scores``' ``tables``);
+                   all D lists have the same T, else ValueError
+    The other arguments are ``split_scores``'.  Returns a ``SplitScores`` whose
+    ``fair_mean_diff`` and ``fair_mean_sq`` are (D,) and whose ``fair_terms``
+    is (D, T, G); ``miF1``, ``maF1``, ``counts`` and ``gid`` do not depend on
+    the definitions.  Every definition's numbers are, bit for bit, what
+    ``split_scores`` gives for that definition alone (same ``slices``): one
+    weights call on the D T sources, then one mpv_split_eval_defs.  A
+    definition with no active term holds NaN.  No host sync.  CPU tensors run
+    ``split_scores``' torch formulas per definition."""
+    defs = [list(d) for d in definitions]
+    D = len(defs)
+    T = len(defs[0]) if defs else 0
+    if any(len(d) != T for d in defs):
+        raise ValueError("split_scores_defs needs the same number of targets in every definition "
+                         f"(got {[len(d) for d in defs]})")
+    if sensitive_feat is None or centroids is None:
+        raise ValueError("split_scores_defs needs sensitive_feat and centroids")
+    dev = pred.device
+    host = dev.type == "cpu"
+    used = (pred, labels, sensitive_feat, centroids, weight_labels)
+    if host:
+        if any(t is not None and t.device.type != "cpu" for t in used):
+            raise RuntimeError("split_scores_defs inputs must all live on one device")
+        if D == 0:
+            raise ValueError("split_scores_defs needs at least one definition")
+    else:
+        H.require_gpu(*used)
+    p = pred.detach().contiguous().float()
+    y = labels.detach().contiguous().float()
+    N, L = p.shape
+    if tuple(y.shape) != (N, L):
+        raise ValueError(f"labels {tuple(y.shape)} do not match pred {(N, L)}")
+    G = centroids.shape[0]
+    nan = torch.full((), float("nan"), dtype=torch.float64, device=dev)
+    if N == 0:  # shapes are host knowledge: no launch with an empty grid
+        return SplitScores(nan, nan.clone(), nan.expand(D).clone(), nan.expand(D).clone(),
+                           torch.full((D, T, G), float("nan"), dtype=torch.float64, device=dev),
+                           torch.zeros((3, L), dtype=torch.float64, device=dev),
+                           torch.zeros(0, dtype=torch.int32, device=dev))
+    gid, unmatched = centroid_ids(sensitive_feat, centroids)
+    wl = y if weight_labels is None else weight_labels.detach().contiguous().float()
+    if tuple(wl.shape) != (N, L):
+        raise ValueError(f"weight_labels {tuple(wl.shape)} do not match pred {(N, L)}")
+    flat = [s for d in defs for s in d]
+    if host:
+        w = _weights_host(wl, flat).reshape(D, T, N) if T else None
+        per = [_split_scores_host(p, y, None if w is None else w[d], gid, G) for d in range(D)]
+        counts, out = per[0][0], per[0][1]
+        out_defs = torch.stack([o[2:5] for _, o, _ in per])
+        terms = torch.stack([t for _, _, t in per]) if T else torch.empty((D, 0, G),
+                                                                          dtype=torch.float64)
+    else:
+        w = label_weights_batch(wl, flat)[0] if flat else None
+        order, goff = _group_layout(gid, G)
+        R = eval_slices(N, L, G, dev) if slices is None else int(slices)
+        counts, out, out_defs, terms = _split_eval_defs(p, y, w, order, goff, G, R, D, T)
+    return SplitScores(out[0], out[1], torch.where(unmatched, nan, out_defs[:, 0]),
+                       torch.where(unmatched, nan, out_defs[:, 1]),
                        torch.where(unmatched, torch.full_like(terms, float("nan")), terms),
                        counts, gid)

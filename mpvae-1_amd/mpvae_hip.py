@@ -13,7 +13,7 @@ import torch  # noqa: F401  (must precede the .so load: one HIP runtime per proc
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MPVAE_HIP_LIB", os.path.join(HERE, "libmpvae_hip.so"))
 
-ABI_VERSION = 16
+ABI_VERSION = 17
 F32, F64 = 0, 1
 G_TOTAL, G_NLL, G_NLL_X, G_C, G_C_X, G_KL = range(6)
 
@@ -98,6 +98,15 @@ class LabelTable(ctypes.Structure):
                 ("W", ctypes.c_int64)]
 
 
+class LabelSim(ctypes.Structure):
+    """mpv_label_sim: a closed-form label similarity to a packed target (fairness.hip)."""
+    _fields_ = [("target", vp), ("kind", ctypes.c_int32), ("has_gamma", ctypes.c_int32),
+                ("gamma", ctypes.c_double), ("clip_lo", ctypes.c_double),
+                ("clip_hi", ctypes.c_double)]
+
+
+SIM_INDICATION, SIM_CONSTANT, SIM_JACCARD, SIM_HAMMING = range(4)  # mpv_sim_kind
+LABEL_SIMS_PER_LAUNCH = 8  # MPV_LABEL_SIMS_PER_LAUNCH
 FAIR_L1, FAIR_L2 = 1, 2
 LABEL_TABLES_PER_LAUNCH = 8  # MPV_LABEL_TABLES_PER_LAUNCH
 EL_F32, EL_F64, EL_I32, EL_I64 = range(4)  # mpv_elem
@@ -231,6 +240,9 @@ SIGNATURES = {
     "mpv_label_weights_batch": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.c_int64,
                                                ctypes.POINTER(LabelTable), ctypes.c_int64, vp, vp,
                                                vp]),
+    "mpv_label_sim_weights": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.c_int64,
+                                             ctypes.POINTER(LabelSim), ctypes.c_int64, vp, vp,
+                                             vp]),
     "mpv_group_rows": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
                                       ctypes.c_int64, vp, vp, vp, vp, vp]),
     "mpv_fair_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64,
@@ -254,6 +266,8 @@ SIGNATURES = {
                                      vp]),
     "mpv_split_eval_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64] * 5),
     "mpv_split_eval": (ctypes.c_int, [ctypes.POINTER(SplitEvalArgs), vp, ctypes.c_size_t, vp]),
+    "mpv_split_eval_defs": (ctypes.c_int, [ctypes.POINTER(SplitEvalArgs), ctypes.c_int64, vp, vp,
+                                           ctypes.c_size_t, vp]),
 }
 
 _lib = None
@@ -315,7 +329,7 @@ def require_gpu(*tensors):
 
 KERNELS = ["noise_philox", "split", "probit_fwd", "fwd_combine", "finalize", "bwd_coef", "bwd_elem",
            "dR_gemm", "sum_slabs", "convert", "bstat_combine", "reparam_fwd", "reparam_bwd",
-           "kl_bwd", "label_weights", "group_rows", "fair_fwd", "fair_bwd", "metrics", "linear", "adam",
+           "kl_bwd", "label_weights", "label_sim", "group_rows", "fair_fwd", "fair_bwd", "metrics", "linear", "adam",
            "adam_finish", "curve_keys", "curve_sort", "curve_merge", "curve_pass", "curve_agg",
            "metric_sweep", "calib_fwd", "calib_tables", "calib_bwd", "probit_predict",
            "predict_final", "split_eval", "split_final"]

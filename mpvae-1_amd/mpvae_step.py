@@ -705,7 +705,12 @@ class EvalPass:
     (``mpvae_seed_advance``, as TrainStep does), so every batch draws fresh
     noise.  ``tables``, ``centroids``, ``weight_labels`` and ``slices`` are
     those of ``split_scores`` -- see there for the reference's choice of the
-    rows its weights are looked up by.  The model is put in ``eval()`` mode
+    rows its weights are looked up by.  ``definitions`` (instead of ``tables``:
+    D lists of T weight sources each, as ``mpvae_fair.split_scores_defs`` takes
+    them) scores the one (N, L) buffer under all D definitions -- the sweep of
+    fairsoft_metric.evaluate_models_over_label_distances from one pass over
+    the split; ``read`` then returns ``fair_mean_diff`` as a list of D floats,
+    still with one host sync.  The model is put in ``eval()`` mode
     under ``no_grad`` and its previous mode is restored.
 
     With Philox noise and a device seed nothing in ``run`` waits for the host,
@@ -716,13 +721,16 @@ class EvalPass:
     libmpvae_host.so and the scoring in torch (``split_scores``)."""
 
     def __init__(self, model, args, batch_size, tables=None, centroids=None, label_free=False,
-                 slices=None):
+                 slices=None, definitions=None):
         if int(batch_size) < 1:
             raise ValueError(f"batch_size must be >= 1 (got {batch_size})")
-        if tables is not None and centroids is None:
+        if tables is not None and definitions is not None:
+            raise ValueError("EvalPass takes tables or definitions, not both")
+        if (tables is not None or definitions is not None) and centroids is None:
             raise ValueError("EvalPass with tables needs the dataset's centroids")
         self.model, self.args, self.batch_size = model, args, int(batch_size)
         self.tables = None if tables is None else list(tables)
+        self.definitions = None if definitions is None else [list(d) for d in definitions]
         self.centroids, self.label_free, self.slices = centroids, bool(label_free), slices
         self.graph = None
         self.label = self.feat = self.out = None
@@ -745,7 +753,7 @@ class EvalPass:
 
     def run(self, labels, feats, sensitive_feat=None, weight_labels=None):
         import mpvae_fair
-        if self.tables is not None and sensitive_feat is None:
+        if (self.tables is not None or self.definitions is not None) and sensitive_feat is None:
             raise ValueError("EvalPass with tables needs the split's sensitive_feat")
         N, L = labels.shape
         B = self.batch_size
@@ -765,8 +773,13 @@ class EvalPass:
                         buf[s:e].copy_(self.out)
                     else:
                         buf[s:e].copy_(self._batch(labels[s:e].float(), feats[s:e]))
-                scores = mpvae_fair.split_scores(buf, labels, sensitive_feat, self.centroids,
-                                                 self.tables, weight_labels, self.slices)
+                if self.definitions is not None:
+                    scores = mpvae_fair.split_scores_defs(buf, labels, sensitive_feat,
+                                                          self.centroids, self.definitions,
+                                                          weight_labels, self.slices)
+                else:
+                    scores = mpvae_fair.split_scores(buf, labels, sensitive_feat, self.centroids,
+                                                     self.tables, weight_labels, self.slices)
         finally:
             self.model.train(was_training)
         return EvalOut(buf, scores)
@@ -807,6 +820,9 @@ class EvalPass:
     def read(out):
         """The reference's result dict as Python floats, with one host sync."""
         s = out.scores
+        if s.fair_mean_diff is not None and s.fair_mean_diff.dim() == 1:  # definitions
+            vals = torch.cat([torch.stack([s.miF1, s.maF1]), s.fair_mean_diff]).cpu().tolist()
+            return {"fair_mean_diff": vals[2:], "miF1": vals[0], "maF1": vals[1]}
         vals = step_scalars(miF1=s.miF1, maF1=s.maF1,
                             **({} if s.fair_mean_diff is None
                                else {"fair_mean_diff": s.fair_mean_diff}))
