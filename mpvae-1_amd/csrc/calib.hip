@@ -54,15 +54,6 @@ static CalibWs calib_ws(void* ws, int64_t L, int64_t T, int64_t G, int64_t R) {
   return c;
 }
 
-// Slice r of R of group k's positions in `order`: [j0, j1), clipped to [0, B].
-MPV_DEV void calib_slice(const int32_t* __restrict__ goff, int k, int r, int R, int B, int& j0,
-                         int& j1) {
-  const int g0 = min(max(goff[k], 0), B), g1 = min(max(goff[k + 1], g0), B);
-  const int per = (g1 - g0 + R - 1) / R;
-  j0 = min(g0 + r * per, g1);
-  j1 = min(j0 + per, g1);
-}
-
 // The threshold of (label l, group k) and what the calibration needs of it:
 // c = logit(thr) (:40), and for the backward d c / d threshold_.
 struct CalibThr {
@@ -88,25 +79,13 @@ MPV_DEV double calib_q(double p, double c, double& e) {
   return 1.0 / (e + 1.0);
 }
 
-// Block sum in a fixed order (shuffle tree, then the waves in order); thread 0
-// holds the result.
-MPV_DEV double calib_block_sum(double v, double* red) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = 0.0;
-  for (int i = 0; i < kCalThreads / 64; ++i) s += red[i];
-  return s;
-}
-
 __global__ __launch_bounds__(kCalThreads) void calib_fwd_kernel(mpv_calib_args a, CalibWs ws) {
   __shared__ double red[kCalThreads / 64];
   const int L = (int)a.L, B = (int)a.B, T = (int)a.T, G = (int)a.G, R = (int)a.R;
   const int k = blockIdx.y, r = blockIdx.z;
   const int l = blockIdx.x * kCalThreads + threadIdx.x;
   int j0, j1;
-  calib_slice(a.goff, k, r, R, B, j0, j1);
+  group_slice(a.goff, k, r, R, B, j0, j1);
   double bce = 0.0;
   if (l < L) {
     const bool cal = a.threshold != nullptr;  // else p is already calibrated
@@ -147,7 +126,7 @@ __global__ __launch_bounds__(kCalThreads) void calib_fwd_kernel(mpv_calib_args a
       }
     }
   }
-  bce = calib_block_sum(bce, red);
+  bce = block_sum_f64<kCalThreads / 64>(bce, red);
   if (threadIdx.x == 0) ws.bpart[((int64_t)blockIdx.x * G + k) * R + r] = bce;
 }
 
@@ -157,18 +136,7 @@ __global__ __launch_bounds__(kCalThreads) void calib_tables_kernel(mpv_calib_arg
   __shared__ double red[kCalThreads / 64];
   const int L = (int)a.L, T = (int)a.T, G = (int)a.G, R = (int)a.R;
   const int tid = threadIdx.x;
-  for (int i = tid; i < T * G; i += kCalThreads) {
-    double s = 0.0;
-    for (int r = 0; r < R; ++r) s += ws.wpart[(int64_t)i * R + r];
-    ws.wsum[(i / G) * (G + 1) + i % G] = s;
-  }
-  __syncthreads();
-  for (int t = tid; t < T; t += kCalThreads) {
-    double s = 0.0;
-    for (int k = 0; k < G; ++k) s += ws.wsum[t * (G + 1) + k];
-    ws.wsum[t * (G + 1) + G] = s;
-  }
-  __syncthreads();
+  slice_weight_sums(ws.wpart, ws.wsum, T, G, R);
   double pen = 0.0;
   for (int l = tid; l < L; l += kCalThreads) {
     for (int t = 0; t < T; ++t) {
@@ -184,11 +152,7 @@ __global__ __launch_bounds__(kCalThreads) void calib_tables_kernel(mpv_calib_arg
           if (Wk > 0.0) {  // :157 `if weight_sensitive.sum() > 0`
             double s = 0.0;
             for (int r = 0; r < R; ++r) s += ws.qpart[(((int64_t)t * G + k) * R + r) * L + l];
-            const double d = s / Wk - mt;
-            pen += d * d;
-            fp = 2.0 * d;
-            esum += fp;
-            fp /= Wk;
+            fp = fair_pair_step(s, Wk, mt, MPV_FAIR_L2, pen, esum);
           }
           ws.dtab[((int64_t)t * G + k) * L + l] = fp;
         }
@@ -199,11 +163,10 @@ __global__ __launch_bounds__(kCalThreads) void calib_tables_kernel(mpv_calib_arg
       ws.etab[(int64_t)t * L + l] = esum;
     }
   }
-  pen = calib_block_sum(pen, red);
-  __syncthreads();  // `red` is reused below
+  pen = block_sum_f64<kCalThreads / 64>(pen, red);
   double bce = 0.0;
   for (int i = tid; i < nlb * G * R; i += kCalThreads) bce += ws.bpart[i];
-  bce = calib_block_sum(bce, red);
+  bce = block_sum_f64<kCalThreads / 64>(bce, red);
   if (tid == 0) {
     int nterms = 0;
     for (int t = 0; t < T; ++t) {
@@ -224,7 +187,7 @@ __global__ __launch_bounds__(kCalThreads) void calib_bwd_kernel(mpv_calib_args a
   const int l = blockIdx.x * kCalThreads + threadIdx.x;
   if (l >= L) return;
   int j0, j1;
-  calib_slice(a.goff, k, r, R, B, j0, j1);
+  group_slice(a.goff, k, r, R, B, j0, j1);
   const CalibThr th = calib_thr((double)a.threshold[(int64_t)l * G + k], a.learn_logit);
   const double gb = a.y != nullptr ? gout[0] / (double)B : 0.0, gf = gout[1];
   // D[t, k, l] - E[t, l] of the first kCalTile targets in registers

@@ -155,20 +155,6 @@ __global__ __launch_bounds__(kMergeThreads) void curve_merge_kernel(
 constexpr int kCurveThreads = 256, kCurveItems = 4, kCurveTile = kCurveThreads * kCurveItems;
 constexpr int kCurveWaves = kCurveThreads / 64;
 
-// Sum of v over the workgroup in a fixed order (shuffle tree, then the waves in
-// order); every thread gets it.  `red` holds one double per wave.
-MPV_DEV double block_sum_f64(double v, double* red) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = 0.0;
-  const int nw = (blockDim.x + 63) >> 6;
-  for (int i = 0; i < nw; ++i) s += red[i];
-  return s;
-}
-
 MPV_DEV uint64_t shfl_up_u64(uint64_t v, int o) {
   return (uint64_t)__shfl_up((unsigned long long)v, o, 64);
 }
@@ -270,8 +256,8 @@ __global__ __launch_bounds__(kCurveThreads) void curve_pass_kernel(
     carry_t += tile_t;
     carry_e = tile_e > carry_e ? tile_e : carry_e;
   }
-  const double t_auc = block_sum_f64(s_auc, red);
-  const double t_pr = block_sum_f64(s_pr, red);
+  const double t_auc = block_sum_f64<kCurveWaves>(s_auc, red);
+  const double t_pr = block_sum_f64<kCurveWaves>(s_pr, red);
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) {
     const uint64_t x = shfl_xor_u64(best, o);
@@ -309,14 +295,15 @@ __global__ __launch_bounds__(kSortThreads) void curve_agg_kernel(const double* _
     cnt += ok ? 1.0 : 0.0;
     sum += ok ? x : 0.0;
   }
-  const double kept = block_sum_f64(cnt, red);  // a count <= 4096: exact
-  const double mean = block_sum_f64(sum, red) / kept;
+  const double kept = block_sum_f64<kSortThreads / 64>(cnt, red);  // a count <= 4096: exact
+  const double mean = block_sum_f64<kSortThreads / 64>(sum, red) / kept;
   double q = 0.0;
   for (int i = tid; i < L; i += kSortThreads) {
     const double x = v[i];
     if (x == x) q += (x - mean) * (x - mean);
   }
-  const double var = block_sum_f64(q, red) / kept;  // also the barrier after the writes of s
+  // also the barrier after the writes of s
+  const double var = block_sum_f64<kSortThreads / 64>(q, red) / kept;
   for (int k = 2; k <= m; k <<= 1) {
     for (int j = k >> 1; j > 0; j >>= 1) {
       for (int t = tid; t < (m >> 1); t += kSortThreads) {

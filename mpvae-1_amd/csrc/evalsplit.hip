@@ -76,20 +76,6 @@ static int eval_lanes(int64_t L) {
   return lp;
 }
 
-// Slice r of R of group k's positions: [j0, j1), clipped to [0, N].  Without
-// goff there is one group, every position.
-MPV_DEV void eval_slice(const int32_t* __restrict__ goff, int k, int r, int R, int N, int& j0,
-                        int& j1) {
-  int g0 = 0, g1 = N;
-  if (goff != nullptr) {
-    g0 = min(max(goff[k], 0), N);
-    g1 = min(max(goff[k + 1], g0), N);
-  }
-  const int per = (g1 - g0 + R - 1) / R;
-  j0 = min(g0 + r * per, g1);
-  j1 = min(j0 + per, g1);
-}
-
 // The sums of v[] over the lanes that share a label, in a fixed order: the
 // rows of a wave by a shuffle tree, then the waves in order.  Threads
 // 0 .. lp - 1 hold the result.
@@ -125,7 +111,7 @@ __global__ __launch_bounds__(kEvalThreads) void split_eval_kernel(mpv_split_eval
   const int row = tid / lp, rows = kEvalThreads / lp;
   const bool live = l < L;
   int j0, j1;
-  eval_slice(a.goff, k, r, R, N, j0, j1);
+  group_slice(a.goff, k, r, R, N, j0, j1);
   for (int t0 = 0; t0 < max(T, 1); t0 += kEvalTile) {
     double v[kEvalVals];
 #pragma unroll
@@ -168,19 +154,6 @@ __global__ __launch_bounds__(kEvalThreads) void split_eval_kernel(mpv_split_eval
   }
 }
 
-// Block sum in a fixed order (shuffle tree, then the waves in order); every
-// thread holds the result.
-MPV_DEV double eval_sum(double v, double* red) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();  // `red` may still be read from the sum before
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = 0.0;
-  for (int i = 0; i < kEvalWaves; ++i) s += red[i];
-  return s;
-}
-
 // One block.  The workspace's tables are written and read back by this block
 // alone, with a barrier between the phases.
 //
@@ -198,12 +171,7 @@ __global__ __launch_bounds__(kEvalThreads) void split_final_kernel(mpv_split_eva
   const int64_t L = a.L, T = a.T, G = a.G, R = a.R;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const double nan = __longlong_as_double(0x7ff8000000000000ll);
-  // W_tk, then W_t
-  for (int64_t i = tid; i < T * G; i += kEvalThreads) {
-    double s = 0.0;
-    for (int64_t r = 0; r < R; ++r) s += ws.wpart[i * R + r];
-    ws.wsum[(i / G) * (G + 1) + i % G] = s;
-  }
+  slice_weight_sums(ws.wpart, ws.wsum, T, G, R);
   // the slices of every (t, k, l) and (k, c, l), r in order
   for (int64_t i = tid; i < T * G * L; i += kEvalThreads) {
     const int64_t tk = i / L, l = i % L;
@@ -216,12 +184,6 @@ __global__ __launch_bounds__(kEvalThreads) void split_final_kernel(mpv_split_eva
     double s = 0.0;
     for (int64_t r = 0; r < R; ++r) s += ws.cpart[(k * R + r) * 3 * L + cl];
     ws.csum[i] = s;
-  }
-  __syncthreads();
-  for (int64_t t = tid; t < T; t += kEvalThreads) {
-    double s = 0.0;
-    for (int64_t k = 0; k < G; ++k) s += ws.wsum[t * (G + 1) + k];
-    ws.wsum[t * (G + 1) + G] = s;
   }
   __syncthreads();
   // m_t and the counts, k in order
@@ -249,8 +211,7 @@ __global__ __launch_bounds__(kEvalThreads) void split_final_kernel(mpv_split_eva
         s += d * d;
       }
     }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o, 64);
+    s = wave_sum(s);
     if (lane == 0) a.terms[i] = (Wt > 0.0 && Wk > 0.0) ? s : nan;
   }
   __syncthreads();
@@ -265,9 +226,9 @@ __global__ __launch_bounds__(kEvalThreads) void split_final_kernel(mpv_split_eva
         cnt += 1.0;
       }
     }
-    dist = eval_sum(dist, red);
-    sq = eval_sum(sq, red);
-    cnt = eval_sum(cnt, red);
+    dist = block_sum_f64<kEvalWaves>(dist, red);
+    sq = block_sum_f64<kEvalWaves>(sq, red);
+    cnt = block_sum_f64<kEvalWaves>(cnt, red);
     if (tid == 0) {
       double* o = out_defs != nullptr ? out_defs + 3 * d : a.out + 2;
       o[0] = dist / cnt;  // np.mean([]) is NaN
@@ -292,11 +253,11 @@ __global__ __launch_bounds__(kEvalThreads) void split_final_kernel(mpv_split_eva
       nf += 1.0;
     }
   }
-  tp = eval_sum(tp, red);
-  fp = eval_sum(fp, red);
-  fn = eval_sum(fn, red);
-  f1 = eval_sum(f1, red);
-  nf = eval_sum(nf, red);
+  tp = block_sum_f64<kEvalWaves>(tp, red);
+  fp = block_sum_f64<kEvalWaves>(fp, red);
+  fn = block_sum_f64<kEvalWaves>(fn, red);
+  f1 = block_sum_f64<kEvalWaves>(f1, red);
+  nf = block_sum_f64<kEvalWaves>(nf, red);
   if (tid == 0) {
     a.out[0] = 2.0 * tp / (2.0 * tp + fp + fn);  // evals.py:99-100
     a.out[1] = f1 / nf;                          // np.mean of the kept labels; none: NaN

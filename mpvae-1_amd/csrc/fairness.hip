@@ -1,21 +1,19 @@
 // The two per-step consumers of compute_loss's indiv_prob outputs in the
 // reference training loop, on the device:
 //
-//   label_weights_kernel   per-row weight = label_distances[target].get(
-//                          ''.join(label.astype(str)), 0.)  (fairsoft_train.py:
-//                          85-93): the row's 0/1 label pattern is packed by
-//                          wave ballots and looked up in an open-addressing
-//                          table of packed patterns (built once on the host
-//                          from the same dict), instead of a Python string join
-//                          and dict lookup per row.
-//   label_weights_batch_   the same for up to MPV_LABEL_TABLES_PER_LAUNCH target
-//   kernel                 tables in one launch: the row packed and hashed once.
-//   label_sim_kernel       the weights without a dict: indication, constant,
-//                          Jaccard and Hamming similarity to a packed target
-//                          (label_distance_obs.py:9-168, with dist_gamma the
-//                          clipped exponential) from popcounts of the packed
-//                          row, up to MPV_LABEL_SIMS_PER_LAUNCH definitions a
-//                          launch.
+//   row_weights_kernel     per-row weights of up to 8 sources a launch, the row's
+//                          0/1 label pattern packed by wave ballots once.  A
+//                          template over the source set.  LabelTables: weight =
+//                          label_distances[target].get(''.join(label.astype(
+//                          str)), 0.) (fairsoft_train.py:85-93), the pattern
+//                          looked up in an open-addressing table of packed
+//                          patterns (built once on the host from the same dict)
+//                          instead of a Python string join and dict lookup per
+//                          row.  LabelSims: the weights without a dict:
+//                          indication, constant, Jaccard and Hamming similarity
+//                          to a packed target (label_distance_obs.py:9-168, with
+//                          dist_gamma the clipped exponential) from popcounts
+//                          of the packed row.
 //   group_rows_kernel      the batch's sensitive groups (torch.unique(x, dim=0)'s
 //                          inverse, fairsoft_train.py:81, :106-111) with the
 //                          stable order by group and the group offsets, in one
@@ -92,70 +90,32 @@ MPV_DEV double probe_table(const mpv_label_table& tab, uint64_t h, const uint64_
   return 0.0;
 }
 
-__global__ __launch_bounds__(64 * kLwWaves) void label_weights_kernel(
-    const float* __restrict__ y, int B, int L, mpv_label_table tab, double* __restrict__ w,
-    int* __restrict__ contributed) {
-  __shared__ uint64_t words[kLwWaves][64];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int b = blockIdx.x * kLwWaves + wv;
-  if (b >= B) return;
-  uint64_t h;
-  const bool bad = pack_row(y, b, L, (int)tab.W, words[wv], h);
-  const double val = bad ? 0.0 : probe_table(tab, h, words[wv]);
-  if (lane == 0) {
-    w[b] = val;
-    if (val > 0.0) atomicAdd(contributed, 1);  // integer count: order-free
-  }
-}
-
-// Up to MPV_LABEL_TABLES_PER_LAUNCH target tables by value: the row is packed
-// and hashed once, then probed in every table (w row t of this chunk).
+// A set of up to N weight sources passed by value, rows t = 0 .. n - 1 of a
+// launch's w.  The two kinds differ in weight() alone: the value of source i
+// for the packed row (`words` in LDS with hash h; `row` is lane's word, 0 past
+// W), the whole wave calling.
+//
+// Target tables (mpv_label_weights: N = 1; mpv_label_weights_batch): the row
+// is packed and hashed once, then probed in every table.
+template <int N>
 struct LabelTables {
-  mpv_label_table t[MPV_LABEL_TABLES_PER_LAUNCH];
+  mpv_label_table s[N];
   int n;
+  MPV_DEV double weight(int i, uint64_t h, const uint64_t* words, uint64_t, int) const {
+    return probe_table(s[i], h, words);
+  }
 };
 
-__global__ __launch_bounds__(64 * kLwWaves) void label_weights_batch_kernel(
-    const float* __restrict__ y, int B, int L, LabelTables tabs, double* __restrict__ w,
-    int* __restrict__ contributed) {
-  __shared__ uint64_t words[kLwWaves][64];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int b = blockIdx.x * kLwWaves + wv;
-  if (b >= B) return;
-  uint64_t h;
-  const bool bad = pack_row(y, b, L, (int)tabs.t[0].W, words[wv], h);
-  int positive = 0;
-  for (int t = 0; t < tabs.n; ++t) {
-    const double val = bad ? 0.0 : probe_table(tabs.t[t], h, words[wv]);
-    if (lane == 0) w[(int64_t)t * B + b] = val;
-    positive += val > 0.0;
-  }
-  if (lane == 0 && positive) atomicAdd(contributed, positive);  // integer count: order-free
-}
-
-// Up to MPV_LABEL_SIMS_PER_LAUNCH similarity definitions by value: the weight
-// is a closed form of the row's and the target's bit patterns (what the
-// builders of label_distance_obs.py store per pair of label strings), so the
-// row is packed once and every definition costs three popcounts per word.
+// Similarity definitions: the weight is a closed form of the row's and the
+// target's bit patterns (what the builders of label_distance_obs.py store per
+// pair of label strings), three popcounts per word.
 struct LabelSims {
   mpv_label_sim s[MPV_LABEL_SIMS_PER_LAUNCH];
   int n;
-};
-
-__global__ __launch_bounds__(64 * kLwWaves) void label_sim_kernel(
-    const float* __restrict__ y, int B, int L, int W, LabelSims sims, double* __restrict__ w,
-    int* __restrict__ contributed) {
-  __shared__ uint64_t words[kLwWaves][64];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int b = blockIdx.x * kLwWaves + wv;
-  if (b >= B) return;
-  uint64_t h;
-  const bool bad = pack_row(y, b, L, W, words[wv], h);
-  const uint64_t row = lane < W ? words[wv][lane] : 0;
-  int positive = 0;
-  for (int t = 0; t < sims.n; ++t) {
-    const mpv_label_sim& s = sims.s[t];
-    const uint64_t tgt = lane < W ? s.target[lane] : 0;
+  MPV_DEV double weight(int i, uint64_t, const uint64_t*, uint64_t row, int L) const {
+    const int lane = threadIdx.x & 63, W = (L + 63) / 64;
+    const mpv_label_sim& d = s[i];
+    const uint64_t tgt = lane < W ? d.target[lane] : 0;
     int n_and = __popcll(row & tgt), n_or = __popcll(row | tgt), n_xor = __popcll(row ^ tgt);
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) {  // integer sums: order-free
@@ -164,18 +124,34 @@ __global__ __launch_bounds__(64 * kLwWaves) void label_sim_kernel(
       n_xor += __shfl_xor(n_xor, o, 64);
     }
     double sim = 1.0;  // MPV_SIM_CONSTANT
-    if (s.kind == MPV_SIM_INDICATION) {
+    if (d.kind == MPV_SIM_INDICATION) {
       sim = n_xor == 0 ? 1.0 : 0.0;
-    } else if (s.kind == MPV_SIM_JACCARD) {  // unequal patterns have n_or > 0
+    } else if (d.kind == MPV_SIM_JACCARD) {  // unequal patterns have n_or > 0
       sim = n_xor == 0 ? 1.0 : (double)n_and / (double)n_or;
-    } else if (s.kind == MPV_SIM_HAMMING) {
+    } else if (d.kind == MPV_SIM_HAMMING) {
       sim = (double)(L - n_xor) / (double)L;
     }
-    double val = sim;
     // np.clip(np.exp(gamma * (sim - 1)), lo, hi): subtract, then multiply, so
     // nothing is contracted and exp sees numpy's argument
-    if (s.has_gamma) val = fmin(fmax(exp(s.gamma * (sim - 1.0)), s.clip_lo), s.clip_hi);
-    if (bad) val = 0.0;
+    if (d.has_gamma) return fmin(fmax(exp(d.gamma * (sim - 1.0)), d.clip_lo), d.clip_hi);
+    return sim;
+  }
+};
+
+template <typename Set>
+__global__ __launch_bounds__(64 * kLwWaves) void row_weights_kernel(
+    const float* __restrict__ y, int B, int L, Set set, double* __restrict__ w,
+    int* __restrict__ contributed) {
+  __shared__ uint64_t words[kLwWaves][64];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, W = (L + 63) / 64;
+  const int b = blockIdx.x * kLwWaves + wv;
+  if (b >= B) return;
+  uint64_t h;
+  const bool bad = pack_row(y, b, L, W, words[wv], h);
+  const uint64_t row = lane < W ? words[wv][lane] : 0;
+  int positive = 0;
+  for (int t = 0; t < set.n; ++t) {
+    const double val = bad ? 0.0 : set.weight(t, h, words[wv], row, L);
     if (lane == 0) w[(int64_t)t * B + b] = val;
     positive += val > 0.0;
   }
@@ -307,16 +283,7 @@ __global__ __launch_bounds__(kFairThreads) void fair_fwd_kernel(mpv_fair_args a,
               const int b = a.order[j];
               s += (double)z[(int64_t)b * L + l] * wt[b];
             }
-            const double d = s / Wk - mt;
-            if (a.norm == MPV_FAIR_L1) {
-              pen += fabs(d);
-              fp = d > 0.0 ? 1.0 : (d < 0.0 ? -1.0 : 0.0);
-            } else if (a.norm == MPV_FAIR_L2) {
-              pen += d * d;
-              fp = 2.0 * d;
-            }
-            esum += fp;
-            fp /= Wk;
+            fp = fair_pair_step(s, Wk, mt, a.norm, pen, esum);
           }
           dtab[(((int64_t)br * T + t) * G + k) * L + l] = fp;
         }
@@ -327,16 +294,8 @@ __global__ __launch_bounds__(kFairThreads) void fair_fwd_kernel(mpv_fair_args a,
       etab[((int64_t)br * T + t) * L + l] = esum;
     }
   }
-  // block sum of pen (fixed shuffle tree, then the 4 waves in order)
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) pen += __shfl_xor(pen, o, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = pen;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double s = 0.0;
-    for (int i = 0; i < kFairThreads / 64; ++i) s += red[i];
-    part[blockIdx.y * gridDim.x + blockIdx.x] = s;
-  }
+  pen = block_sum_f64<kFairThreads / 64>(pen, red);
+  if (threadIdx.x == 0) part[blockIdx.y * gridDim.x + blockIdx.x] = pen;
 }
 
 __global__ void fair_final_kernel(const double* __restrict__ part, int n, double coeff,
@@ -528,6 +487,26 @@ static int check_label_table(const mpv_label_table* tab, int64_t L) {
   return MPV_OK;
 }
 
+// T sources in launches of a Set's capacity each, chunk t0 filling rows t0 ..
+// of w (the unused slots of the last chunk repeat its first source).  `tag` is
+// the timing label, `what` names the launch in an error.
+template <typename Set, typename Src>
+static int launch_row_weights(const char* tag, const char* what, const float* y, int64_t B,
+                              int64_t L, const Src* src, int64_t T, double* w,
+                              int32_t* contributed, void* stream) {
+  constexpr int64_t cap = sizeof(Set::s) / sizeof(Src);
+  const int blocks = (int)cdiv(B, kLwWaves);
+  for (int64_t t0 = 0; t0 < T; t0 += cap) {
+    Set set;
+    set.n = (int)(T - t0 < cap ? T - t0 : cap);
+    for (int64_t i = 0; i < cap; ++i) set.s[i] = src[t0 + (i < set.n ? i : 0)];
+    MPV_LAUNCH(tag, row_weights_kernel<Set>, dim3(blocks), dim3(64 * kLwWaves), 0,
+               as_stream(stream), y, (int)B, (int)L, set, w + t0 * B, contributed);
+    if (int rc = check_launch(what)) return rc;
+  }
+  return MPV_OK;
+}
+
 template <typename T>
 static void launch_group_rows(const void* x, int B, int n, int G, int32_t* gid, int32_t* order,
                               int32_t* goff, uint8_t* overflow, hipStream_t st) {
@@ -544,10 +523,8 @@ int mpv_label_weights(const float* y, int64_t B, int64_t L, const mpv_label_tabl
                       double* w, int32_t* contributed, void* stream) {
   MPV_REQUIRE(y && tab && w && contributed && B > 0 && L > 0, "bad label_weights arguments");
   if (int rc = check_label_table(tab, L)) return rc;
-  const int blocks = (int)cdiv(B, kLwWaves);
-  MPV_LAUNCH("label_weights", label_weights_kernel, dim3(blocks), dim3(64 * kLwWaves), 0,
-             as_stream(stream), y, (int)B, (int)L, *tab, w, contributed);
-  return check_launch("label_weights");
+  return launch_row_weights<LabelTables<1>>("label_weights", "label_weights", y, B, L, tab, 1, w,
+                                            contributed, stream);
 }
 
 int mpv_label_weights_batch(const float* y, int64_t B, int64_t L, const mpv_label_table* tables,
@@ -556,17 +533,8 @@ int mpv_label_weights_batch(const float* y, int64_t B, int64_t L, const mpv_labe
               "bad label_weights_batch arguments");
   for (int64_t t = 0; t < T; ++t)  // every table is checked before the first launch
     if (int rc = check_label_table(tables + t, L)) return rc;
-  const int blocks = (int)cdiv(B, kLwWaves);
-  for (int64_t t0 = 0; t0 < T; t0 += MPV_LABEL_TABLES_PER_LAUNCH) {
-    LabelTables tabs;
-    tabs.n = (int)(T - t0 < MPV_LABEL_TABLES_PER_LAUNCH ? T - t0 : MPV_LABEL_TABLES_PER_LAUNCH);
-    for (int i = 0; i < MPV_LABEL_TABLES_PER_LAUNCH; ++i)
-      tabs.t[i] = tables[t0 + (i < tabs.n ? i : 0)];
-    MPV_LAUNCH("label_weights", label_weights_batch_kernel, dim3(blocks), dim3(64 * kLwWaves), 0,
-               as_stream(stream), y, (int)B, (int)L, tabs, w + t0 * B, contributed);
-    if (int rc = check_launch("label_weights_batch")) return rc;
-  }
-  return MPV_OK;
+  return launch_row_weights<LabelTables<MPV_LABEL_TABLES_PER_LAUNCH>>(
+      "label_weights", "label_weights_batch", y, B, L, tables, T, w, contributed, stream);
 }
 
 int mpv_label_sim_weights(const float* y, int64_t B, int64_t L, const mpv_label_sim* sims,
@@ -579,16 +547,8 @@ int mpv_label_sim_weights(const float* y, int64_t B, int64_t L, const mpv_label_
     MPV_REQUIRE(sims[t].kind >= MPV_SIM_INDICATION && sims[t].kind <= MPV_SIM_HAMMING,
                 "similarity %lld: unknown kind %d", (long long)t, (int)sims[t].kind);
   }
-  const int blocks = (int)cdiv(B, kLwWaves), W = (int)cdiv(L, 64);
-  for (int64_t t0 = 0; t0 < T; t0 += MPV_LABEL_SIMS_PER_LAUNCH) {
-    LabelSims chunk;
-    chunk.n = (int)(T - t0 < MPV_LABEL_SIMS_PER_LAUNCH ? T - t0 : MPV_LABEL_SIMS_PER_LAUNCH);
-    for (int i = 0; i < MPV_LABEL_SIMS_PER_LAUNCH; ++i) chunk.s[i] = sims[t0 + (i < chunk.n ? i : 0)];
-    MPV_LAUNCH("label_sim", label_sim_kernel, dim3(blocks), dim3(64 * kLwWaves), 0,
-               as_stream(stream), y, (int)B, (int)L, W, chunk, w + t0 * B, contributed);
-    if (int rc = check_launch("label_sim")) return rc;
-  }
-  return MPV_OK;
+  return launch_row_weights<LabelSims>("label_sim", "label_sim", y, B, L, sims, T, w, contributed,
+                                       stream);
 }
 
 int mpv_group_rows(const void* x, int x_elem, int64_t B, int64_t n, int64_t G, int32_t* gid,

@@ -241,6 +241,26 @@ MPV_DEV float wave_max(float v) {
   for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
+MPV_DEV double wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// fp64 sum over a workgroup of WAVES full waves in a fixed order: the shuffle
+// tree, then the waves in index order.  Every thread returns the total; `red`
+// holds one double per wave and may still be in use by the sum before (the
+// leading barrier).
+template <int WAVES>
+MPV_DEV double block_sum_f64(double v, double* red) {
+  v = wave_sum(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double s = 0.0;
+  for (int i = 0; i < WAVES; ++i) s += red[i];
+  return s;
+}
 
 // Block reduction over up to 1024 threads; `red` must hold >= 16 floats.
 // Every thread returns the total.
@@ -512,6 +532,60 @@ MPV_DEV void box_muller(uint32_t we, uint32_t wo, float& n0, float& n1) {
   const float r = __builtin_amdgcn_sqrtf(-1.3862943611198906f * __builtin_amdgcn_logf(u));  // -2 ln 2
   n0 = r * __builtin_amdgcn_cosf(v);
   n1 = r * __builtin_amdgcn_sinf(v);
+}
+
+// ---- fp64 building blocks of the fairness consumers (fairness.hip, calib.hip,
+// evalsplit.hip) -------------------------------------------------------------
+// Slice r of R of group k's positions in `order`: [j0, j1), clipped to [0, B].
+// Without goff there is one group, every position.
+MPV_DEV void group_slice(const int32_t* __restrict__ goff, int k, int r, int R, int B, int& j0,
+                         int& j1) {
+  int g0 = 0, g1 = B;
+  if (goff != nullptr) {
+    g0 = min(max(goff[k], 0), B);
+    g1 = min(max(goff[k + 1], g0), B);
+  }
+  const int per = (g1 - g0 + R - 1) / R;
+  j0 = min(g0 + r * per, g1);
+  j1 = min(j0 + per, g1);
+}
+
+// The whole workgroup: W_tk = sum_r wpart[t, k, r] into wsum[t (G + 1) + k],
+// then W_t = sum_k W_tk into wsum[t (G + 1) + G], r and k in order.  Ends with
+// a barrier: every thread may read wsum.
+MPV_DEV void slice_weight_sums(const double* __restrict__ wpart, double* __restrict__ wsum,
+                               int64_t T, int64_t G, int64_t R) {
+  for (int64_t i = threadIdx.x; i < T * G; i += blockDim.x) {
+    double s = 0.0;
+    for (int64_t r = 0; r < R; ++r) s += wpart[i * R + r];
+    wsum[(i / G) * (G + 1) + i % G] = s;
+  }
+  __syncthreads();
+  for (int64_t t = threadIdx.x; t < T; t += blockDim.x) {
+    double s = 0.0;
+    for (int64_t k = 0; k < G; ++k) s += wsum[t * (G + 1) + k];
+    wsum[t * (G + 1) + G] = s;
+  }
+  __syncthreads();
+}
+
+// One active (target, group) term of the fairness penalty: s the group's
+// weighted sum and Wk > 0 its weight sum, mt the mean over all rows.  Adds the
+// l1 / l2 distance f(d) of d = s / Wk - mt to pen and f'(d) to esum (|x|' =
+// sgn(x), sgn(0) = 0); returns f'(d) / Wk, the backward's table entry.
+MPV_DEV double fair_pair_step(double s, double Wk, double mt, int norm, double& pen,
+                              double& esum) {
+  const double d = s / Wk - mt;
+  double fp = 0.0;
+  if (norm == MPV_FAIR_L1) {
+    pen += fabs(d);
+    fp = d > 0.0 ? 1.0 : (d < 0.0 ? -1.0 : 0.0);
+  } else if (norm == MPV_FAIR_L2) {
+    pen += d * d;
+    fp = 2.0 * d;
+  }
+  esum += fp;
+  return fp / Wk;
 }
 
 // Compute units of the current device (host side; 256 when it cannot be

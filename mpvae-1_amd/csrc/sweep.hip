@@ -354,11 +354,6 @@ MPV_DEV int64_t sweep_wave_sum_i64(int64_t v) {
   for (int o = 32; o >= 1; o >>= 1) v += (int64_t)__shfl_xor((long long)v, o, 64);
   return v;
 }
-MPV_DEV double sweep_wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // Workgroup j -> out[8 j .. 8 j + 7].  Each sum: thread t adds its items t,
 // t + 256, ... in order, then a shuffle tree, then the waves in order.
@@ -367,7 +362,7 @@ __global__ __launch_bounds__(kSweepThreads) void sweep_final_kernel(
     const double* __restrict__ ef_part, const int64_t* __restrict__ xs_part,
     const int32_t* __restrict__ acc_part, const int32_t* __restrict__ nef_part, int64_t N, int L,
     int n_thr, int64_t blocks, int64_t fin_blocks, double* __restrict__ out) {
-  __shared__ double sd[2][kSweepWaves];
+  __shared__ double sd[kSweepWaves];
   __shared__ int64_t si[10][kSweepWaves];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int j = blockIdx.x;
@@ -401,25 +396,19 @@ __global__ __launch_bounds__(kSweepThreads) void sweep_final_kernel(
       ++v[6];
     }
   }
-  ef = sweep_wave_sum_f64(ef);
-  ma = sweep_wave_sum_f64(ma);
+  const double efs = block_sum_f64<kSweepWaves>(ef, sd);
+  const double mas = block_sum_f64<kSweepWaves>(ma, sd);
 #pragma unroll
   for (int k = 0; k < 10; ++k) v[k] = sweep_wave_sum_i64(v[k]);
   if (lane == 0) {
-    sd[0][wv] = ef;
-    sd[1][wv] = ma;
 #pragma unroll
     for (int k = 0; k < 10; ++k) si[k][wv] = v[k];
   }
   __syncthreads();
   if (tid == 0) {
-    double efs = 0.0, mas = 0.0;
     int64_t s[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    for (int i = 0; i < kSweepWaves; ++i) {
-      efs += sd[0][i];
-      mas += sd[1][i];
+    for (int i = 0; i < kSweepWaves; ++i)
       for (int k = 0; k < 10; ++k) s[k] += si[k][i];
-    }
     const double n = (double)N, tp2 = 2.0 * (double)s[7];
     double* o = out + (int64_t)j * 8;
     o[0] = (double)s[1] / n;

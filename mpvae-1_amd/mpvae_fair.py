@@ -30,7 +30,7 @@ Differences from the reference, none of them numeric:
   differs from the reference's fp32 one by fp32 rounding only
   (tests/golden fair_f6/f7, tests/test_gpu_fair.py);
 * a ``LabelSimilarity`` (the row weights as a closed form of the row's and
-  the target's patterns, label_sim_kernel; accepted wherever a
+  the target's patterns, row_weights_kernel<LabelSims>; accepted wherever a
   ``LabelDistanceTable`` is) gives every binary row its formula weight, where
   the reference's dict holds only the patterns that occur in the dataset and
   ``.get(key, 0.)`` gives 0 for any other.  The two agree for rows taken from
@@ -171,7 +171,7 @@ class LabelSimilarity:
     constant_similarity :28-44, str_jac_similarity :54-69, str_ham_similarity
     :120-127; with ``gamma`` the ``np.clip(np.exp(gamma * (sim - 1)), *clip)``
     of the ``_nonlinear`` builders, :106-108), computed per row on the device
-    (label_sim_kernel) instead of built as a dict over every pair of the
+    (row_weights_kernel<LabelSims>) instead of built as a dict over every pair of the
     dataset's patterns.  Accepted wherever a ``LabelDistanceTable`` is, also
     mixed with tables in one list.
 
@@ -235,6 +235,22 @@ def _source_runs(sources):
     return runs
 
 
+def _weights_prep(labels, sources):
+    """What every row-weights entry point sets up: ``(y, w, count)``, the labels
+    as contiguous fp32, the (T, B) fp64 weights to fill and the zero int32
+    count.  With no row nothing is looked up or launched (no empty grid), so
+    the caller returns ``(w, count)`` as they are; else the sources' label_dim
+    is checked."""
+    H.require_gpu(labels)
+    y = labels.contiguous().float()
+    B, L = y.shape
+    w = torch.empty((len(sources), B), dtype=torch.float64, device=y.device)
+    count = torch.zeros((), dtype=torch.int32, device=y.device)
+    if B:
+        _check_label_dim(sources, L)
+    return y, w, count
+
+
 def _sim_weights_into(y, sims, w, count):
     """mpv_label_sim_weights on contiguous fp32 device labels into rows of w."""
     B, L = y.shape
@@ -245,7 +261,7 @@ def _sim_weights_into(y, sims, w, count):
 
 
 def _sim_weights_host(labels, sims):
-    """``similarity_weights`` on CPU tensors: label_sim_kernel's formulas in
+    """``similarity_weights`` on CPU tensors: row_weights_kernel<LabelSims>'s formulas in
     fp64 torch ops, (T, N).  A row that is not exact 0 / 1 after truncation
     gets 0."""
     y = labels.detach().float().trunc()
@@ -290,12 +306,8 @@ def similarity_weights(labels, sims):
     if labels.device.type == "cpu":
         w = _sim_weights_host(labels, sims)
         return w, (w > 0).sum().to(torch.int32)
-    H.require_gpu(labels)
-    y = labels.contiguous().float()
-    B = y.shape[0]
-    w = torch.empty((len(sims), B), dtype=torch.float64, device=y.device)
-    count = torch.zeros((), dtype=torch.int32, device=y.device)
-    if B == 0:  # no row to weigh: no launch with an empty grid
+    y, w, count = _weights_prep(labels, sims)
+    if y.shape[0] == 0:
         return w, count
     _sim_weights_into(y, sims, w, count)
     return w, count
@@ -306,15 +318,11 @@ def label_weights(labels, tables):
     of (target, row) pairs with a positive weight (fairsoft_train.py:85-93).
     A ``LabelSimilarity`` in the list fills its row from its closed form
     (mpv_label_sim_weights), one launch each."""
-    H.require_gpu(labels)
-    y = labels.contiguous().float()
+    y, w, count = _weights_prep(labels, tables)
     B, L = y.shape
-    w = torch.empty((len(tables), B), dtype=torch.float64, device=y.device)
-    count = torch.zeros((), dtype=torch.int32, device=y.device)
-    if B == 0:  # no row to look up: no launch with an empty grid
+    if B == 0:
         return w, count
     lib, st = H.load_library(), H.stream_of(y.device)
-    _check_label_dim(tables, L)
     for t, tab in enumerate(tables):
         if isinstance(tab, LabelSimilarity):
             _sim_weights_into(y, [tab], w[t], count)
@@ -332,14 +340,10 @@ def label_weights_batch(labels, tables):
     count)``, bit for bit.  A list may mix tables and ``LabelSimilarity``
     objects: every maximal run of one kind is one call (mpv_label_weights_batch
     or mpv_label_sim_weights) that fills the run's rows of w."""
-    H.require_gpu(labels)
-    y = labels.contiguous().float()
+    y, w, count = _weights_prep(labels, tables)
     B, L = y.shape
-    w = torch.empty((len(tables), B), dtype=torch.float64, device=y.device)
-    count = torch.zeros((), dtype=torch.int32, device=y.device)
-    if B == 0 or not tables:  # nothing to look up: no launch with an empty grid
+    if B == 0:
         return w, count
-    _check_label_dim(tables, L)
     for t0, t1, sim in _source_runs(tables):
         if sim:
             _sim_weights_into(y, tables[t0:t1], w[t0], count)
@@ -373,6 +377,17 @@ def group_ids(sensitive_feat):
     return (less & firsts[:, None]).sum(0).to(torch.int32)
 
 
+def _group_layout(gid, G):
+    """(order, goff): the rows listed group by group (a stable sort) and the
+    group offsets, for group ids in [0, G)."""
+    order = torch.argsort(gid, stable=True).to(torch.int32)
+    counts = torch.zeros(G, dtype=torch.int32, device=gid.device)
+    counts.index_add_(0, gid.long(), torch.ones_like(gid))
+    goff = torch.zeros(G + 1, dtype=torch.int32, device=gid.device)
+    goff[1:] = torch.cumsum(counts, 0).to(torch.int32)
+    return order.contiguous(), goff
+
+
 def sensitive_groups(sensitive_feat, max_groups=None):
     """(gid, order, goff, G, overflow): group id per row (``group_ids``), the
     rows listed group by group, and the group offsets, for G group slots.  G is
@@ -390,13 +405,9 @@ def sensitive_groups(sensitive_feat, max_groups=None):
     if G < 1:
         raise ValueError(f"max_groups must be >= 1 (got {max_groups})")
     overflow = (gid >= G).any()
-    gid = gid.clamp(max=G - 1)
-    order = torch.argsort(gid, stable=True).to(torch.int32)
-    counts = torch.zeros(G, dtype=torch.int32, device=gid.device)
-    counts.index_add_(0, gid.long(), torch.ones_like(gid))
-    goff = torch.zeros(G + 1, dtype=torch.int32, device=gid.device)
-    goff[1:] = torch.cumsum(counts, 0).to(torch.int32)
-    return gid.contiguous(), order.contiguous(), goff, G, overflow
+    gid = gid.clamp(max=G - 1).contiguous()
+    order, goff = _group_layout(gid, G)
+    return gid, order, goff, G, overflow
 
 
 _ELEMS = {torch.float32: H.EL_F32, torch.float64: H.EL_F64, torch.int32: H.EL_I32,
@@ -702,14 +713,12 @@ def centroid_ids(sensitive_feat, centroids):
     return gid, ~belong.any(1).all()
 
 
-def _group_layout(gid, G):
-    """(order, goff) of ``sensitive_groups`` for given group ids in [0, G)."""
-    order = torch.argsort(gid, stable=True).to(torch.int32)
-    counts = torch.zeros(G, dtype=torch.int32, device=gid.device)
-    counts.index_add_(0, gid.long(), torch.ones_like(gid))
-    goff = torch.zeros(G + 1, dtype=torch.int32, device=gid.device)
-    goff[1:] = torch.cumsum(counts, 0).to(torch.int32)
-    return order.contiguous(), goff
+def _centroid_groups(sensitive_feat, centroids, layout=True):
+    """``(gid, unmatched, order, goff)``: ``centroid_ids`` and the group layout
+    of its ids over the centroids' G groups (None, None without ``layout``)."""
+    gid, unmatched = centroid_ids(sensitive_feat, centroids)
+    order, goff = _group_layout(gid, centroids.shape[0]) if layout else (None, None)
+    return gid, unmatched, order, goff
 
 
 CALIB_MIN_SLICE = 8    # rows a slice should hold before a group is cut further
@@ -833,8 +842,7 @@ def calibration_loss(indiv_prob, threshold_, input_label, sensitive_feat, centro
         w, count = label_weights(y, tables)
     else:
         w, count = None, torch.zeros((), dtype=torch.int32, device=dev)
-    gid, unmatched = centroid_ids(sensitive_feat, centroids)
-    order, goff = _group_layout(gid, G)
+    _, unmatched, order, goff = _centroid_groups(sensitive_feat, centroids)
     R = calib_slices(B, L, G, dev) if slices is None else int(slices)
     bce, fair, cal_prob, nterms = _Calibration.apply(indiv_prob, threshold_, y, w, order, goff, G,
                                                      R, learn_logit)
@@ -858,8 +866,7 @@ def calibrate(indiv_prob, threshold, sensitive_feat, centroids, slices=None):
     _check_threshold(threshold, L, G)
     if B == 0:
         return torch.empty_like(p)
-    gid, unmatched = centroid_ids(sensitive_feat, centroids)
-    order, goff = _group_layout(gid, G)
+    _, _, order, goff = _centroid_groups(sensitive_feat, centroids)
     R = calib_slices(B, L, G, p.device) if slices is None else int(slices)
     x = threshold.detach().contiguous().float()
     _, cal, _ = _calib_fwd(p, x, None, None, order, goff, G, R, False, True)
@@ -882,8 +889,7 @@ def fair_mean_diff(cal_prob, labels, sensitive_feat, centroids, tables, slices=N
         return nan
     w, _ = label_weights(labels, tables)
     G = centroids.shape[0]
-    gid, unmatched = centroid_ids(sensitive_feat, centroids)
-    order, goff = _group_layout(gid, G)
+    _, unmatched, order, goff = _centroid_groups(sensitive_feat, centroids)
     R = calib_slices(B, L, G, q.device) if slices is None else int(slices)
     out, _, _ = _calib_fwd(q, None, None, w, order, goff, G, R, False, False)
     return torch.where(unmatched | (out[2] == 0), nan, out[1] / out[2])
@@ -934,7 +940,7 @@ def eval_slices(N, L, G, device):
 
 def _table_weights_host(labels, tables):
     """``label_weights`` on CPU tensors, in torch: (T, N) fp64.  A row that is
-    not exact 0 / 1 after truncation gets 0, as in label_weights_kernel."""
+    not exact 0 / 1 after truncation gets 0, as in row_weights_kernel."""
     y = labels.detach().float().trunc()
     N, L = y.shape
     W = (L + 63) // 64
@@ -996,21 +1002,96 @@ def _split_scores_host(p, y, w, gid, G):
     return counts, torch.stack([mi, ma, dist, sq, n]), terms
 
 
-def _split_eval(p, y, w, order, goff, G, R):
-    """mpv_split_eval on contiguous device tensors -> (counts, out, terms)."""
+def _split_eval(p, y, w, order, goff, G, R, D=None):
+    """mpv_split_eval on contiguous device tensors, or with ``D`` definitions
+    (``w`` then holds their D T targets) mpv_split_eval_defs.  Without ``D``
+    -> ``(counts, out (5,), terms)``, terms (T, G), None when T = 0; with ``D``
+    -> ``(counts, out, terms, out_defs)``, terms (D, T, G), out_defs (D, 3)."""
     N, L = p.shape
-    T = 0 if w is None else w.shape[0]
-    lib = H.load_library()
-    nbytes = lib.mpv_split_eval_workspace_bytes(N, L, T, G, R)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=p.device)
+    TT = 0 if w is None else w.shape[0]  # targets in all
+    lib, st = H.load_library(), H.stream_of(p.device)
+    nbytes = lib.mpv_split_eval_workspace_bytes(N, L, TT, G, R)
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=p.device)
     counts = torch.empty((3, L), dtype=torch.float64, device=p.device)
     out = torch.empty(5, dtype=torch.float64, device=p.device)
-    terms = torch.empty((T, G), dtype=torch.float64, device=p.device) if T else None
+    T = TT if D is None else TT // max(D, 1)
+    terms = torch.empty((T, G) if D is None else (D, T, G), dtype=torch.float64, device=p.device)
     a = H.SplitEvalArgs(H.ptr(p), H.ptr(y), H.ptr(w), H.ptr(order), H.ptr(goff), N, L, T, G, R,
-                        H.ptr(counts), H.ptr(terms), H.ptr(out))
-    H.check(lib.mpv_split_eval(ctypes.byref(a), H.ptr(ws), nbytes, H.stream_of(p.device)),
-            "mpv_split_eval")
-    return counts, out, terms
+                        H.ptr(counts), H.ptr(terms) if TT else None, H.ptr(out))
+    if D is None:
+        H.check(lib.mpv_split_eval(ctypes.byref(a), H.ptr(ws), nbytes, st), "mpv_split_eval")
+        return counts, out, terms if T else None
+    out_defs = torch.empty((max(D, 1), 3), dtype=torch.float64, device=p.device)
+    H.check(lib.mpv_split_eval_defs(ctypes.byref(a), D, H.ptr(out_defs), H.ptr(ws), nbytes, st),
+            "mpv_split_eval_defs")
+    return counts, out, terms, out_defs
+
+
+def _split_scores(name, pred, labels, sensitive_feat, centroids, definitions, weight_labels,
+                  slices):
+    """The body of ``split_scores_defs`` (``name`` in the messages), and of
+    ``split_scores`` through its one definition.  ``definitions`` None: no
+    fairness at all, the fairness fields None."""
+    fair = definitions is not None
+    defs = [list(d) for d in definitions] if fair else []
+    D = len(defs)
+    T = len(defs[0]) if defs else 0
+    if any(len(d) != T for d in defs):
+        raise ValueError(f"{name} needs the same number of targets in every definition "
+                         f"(got {[len(d) for d in defs]})")
+    if fair and (sensitive_feat is None or centroids is None):
+        raise ValueError(f"{name} needs sensitive_feat and centroids")
+    dev = pred.device
+    host = dev.type == "cpu"
+    used = (pred, labels) + ((sensitive_feat, centroids, weight_labels) if fair else ())
+    if host:
+        if any(t is not None and t.device.type != "cpu" for t in used):
+            raise RuntimeError(f"{name} inputs must all live on one device")
+        if fair and D == 0:
+            raise ValueError(f"{name} needs at least one definition")
+    else:
+        H.require_gpu(*used)
+    p = pred.detach().contiguous().float()
+    y = labels.detach().contiguous().float()
+    N, L = p.shape
+    if tuple(y.shape) != (N, L):
+        raise ValueError(f"labels {tuple(y.shape)} do not match pred {(N, L)}")
+    G = centroids.shape[0] if fair else 1
+    nan = torch.full((), float("nan"), dtype=torch.float64, device=dev)
+    if N == 0:  # shapes are host knowledge: no launch with an empty grid
+        counts = torch.zeros((3, L), dtype=torch.float64, device=dev)
+        if not fair:
+            return SplitScores(nan, nan.clone(), None, None, None, counts, None)
+        return SplitScores(nan, nan.clone(), nan.expand(D).clone(), nan.expand(D).clone(),
+                           torch.full((D, T, G), float("nan"), dtype=torch.float64, device=dev),
+                           counts, torch.zeros(0, dtype=torch.int32, device=dev))
+    if not fair:
+        if host:
+            counts, out, _ = _split_scores_host(p, y, None, None, G)
+        else:
+            R = eval_slices(N, L, G, dev) if slices is None else int(slices)
+            counts, out, _ = _split_eval(p, y, None, None, None, G, R)
+        return SplitScores(out[0], out[1], None, None, None, counts, None)
+    gid, unmatched, order, goff = _centroid_groups(sensitive_feat, centroids, layout=not host)
+    wl = y if weight_labels is None else weight_labels.detach().contiguous().float()
+    if tuple(wl.shape) != (N, L):
+        raise ValueError(f"weight_labels {tuple(wl.shape)} do not match pred {(N, L)}")
+    flat = [s for d in defs for s in d]
+    if host:
+        w = _weights_host(wl, flat).reshape(D, T, N) if T else None
+        per = [_split_scores_host(p, y, None if w is None else w[d], gid, G) for d in range(D)]
+        counts, out = per[0][0], per[0][1]
+        out_defs = torch.stack([o[2:5] for _, o, _ in per])
+        terms = torch.stack([t for _, _, t in per]) if T else torch.empty((D, 0, G),
+                                                                          dtype=torch.float64)
+    else:
+        w = label_weights_batch(wl, flat)[0] if flat else None
+        R = eval_slices(N, L, G, dev) if slices is None else int(slices)
+        counts, out, terms, out_defs = _split_eval(p, y, w, order, goff, G, R, D)
+    return SplitScores(out[0], out[1], torch.where(unmatched, nan, out_defs[:, 0]),
+                       torch.where(unmatched, nan, out_defs[:, 1]),
+                       torch.where(unmatched, torch.full_like(terms, float("nan")), terms),
+                       counts, gid)
 
 
 def split_scores(pred, labels, sensitive_feat=None, centroids=None, tables=None,
@@ -1044,77 +1125,17 @@ def split_scores(pred, labels, sensitive_feat=None, centroids=None, tables=None,
     reference's ``np.mean([])``), and so does a row that matches no centroid.
     N = 0 returns NaN scores without a launch.
 
-    CUDA tensors run mpv_split_eval (csrc/evalsplit.hip).  CPU tensors run the
+    CUDA tensors run mpv_split_eval, with ``tables`` mpv_split_eval_defs on
+    the one definition (csrc/evalsplit.hip).  CPU tensors run the
     same formulas in fp64 torch ops (the reference evaluates small
     configurations on the CPU; ``mpvae_step.EvalPass`` then runs the model
     through libmpvae_host.so): dispatch by device, never a fallback."""
-    dev = pred.device
-    host = dev.type == "cpu"
-    fair = tables is not None
-    if fair and (sensitive_feat is None or centroids is None):
-        raise ValueError("split_scores with tables needs sensitive_feat and centroids")
-    used = (pred, labels) + ((sensitive_feat, centroids, weight_labels) if fair else ())
-    if host:
-        if any(t is not None and t.device.type != "cpu" for t in used):
-            raise RuntimeError("split_scores inputs must all live on one device")
-    else:
-        H.require_gpu(*used)
-    p = pred.detach().contiguous().float()
-    y = labels.detach().contiguous().float()
-    N, L = p.shape
-    if tuple(y.shape) != (N, L):
-        raise ValueError(f"labels {tuple(y.shape)} do not match pred {(N, L)}")
-    nan = torch.full((), float("nan"), dtype=torch.float64, device=dev)
-    T = len(tables) if fair else 0
-    G = centroids.shape[0] if fair else 1
-    if N == 0:  # shapes are host knowledge: no launch with an empty grid
-        return SplitScores(nan, nan.clone(), nan.clone() if fair else None,
-                           nan.clone() if fair else None,
-                           torch.full((T, G), float("nan"), dtype=torch.float64, device=dev)
-                           if fair else None,
-                           torch.zeros((3, L), dtype=torch.float64, device=dev),
-                           torch.zeros(0, dtype=torch.int32, device=dev) if fair else None)
-    gid = unmatched = order = goff = w = None
-    if fair:
-        gid, unmatched = centroid_ids(sensitive_feat, centroids)
-        wl = y if weight_labels is None else weight_labels.detach().contiguous().float()
-        if tuple(wl.shape) != (N, L):
-            raise ValueError(f"weight_labels {tuple(wl.shape)} do not match pred {(N, L)}")
-        if T:
-            w = _weights_host(wl, tables) if host else label_weights_batch(wl, tables)[0]
-    if host:
-        counts, out, terms = _split_scores_host(p, y, w, gid, G)
-    else:
-        if fair:
-            order, goff = _group_layout(gid, G)
-        R = eval_slices(N, L, G, dev) if slices is None else int(slices)
-        counts, out, terms = _split_eval(p, y, w, order, goff, G, R)
-    if not fair:
-        return SplitScores(out[0], out[1], None, None, None, counts, None)
-    if terms is None:
-        terms = torch.full((0, G), float("nan"), dtype=torch.float64, device=dev)
-    return SplitScores(out[0], out[1], torch.where(unmatched, nan, out[2]),
-                       torch.where(unmatched, nan, out[3]),
-                       torch.where(unmatched, torch.full_like(terms, float("nan")), terms),
-                       counts, gid)
-
-
-def _split_eval_defs(p, y, w, order, goff, G, R, D, T):
-    """mpv_split_eval_defs on contiguous device tensors -> (counts, out (5,),
-    out_defs (D, 3), terms (D, T, G))."""
-    N, L = p.shape
-    lib = H.load_library()
-    nbytes = lib.mpv_split_eval_workspace_bytes(N, L, D * T, G, R)
-    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=p.device)
-    counts = torch.empty((3, L), dtype=torch.float64, device=p.device)
-    out = torch.empty(5, dtype=torch.float64, device=p.device)
-    out_defs = torch.empty((max(D, 1), 3), dtype=torch.float64, device=p.device)
-    terms = torch.empty((D, T, G), dtype=torch.float64, device=p.device)
-    a = H.SplitEvalArgs(H.ptr(p), H.ptr(y), H.ptr(w), H.ptr(order), H.ptr(goff), N, L, T, G, R,
-                        H.ptr(counts), H.ptr(terms) if D * T else None, H.ptr(out))
-    H.check(lib.mpv_split_eval_defs(ctypes.byref(a), D, H.ptr(out_defs), H.ptr(ws), nbytes,
-                                    H.stream_of(p.device)), "mpv_split_eval_defs")
-    return counts, out, out_defs, terms
+    sc = _split_scores("split_scores", pred, labels, sensitive_feat, centroids,
+                       None if tables is None else [tables], weight_labels, slices)
+    if tables is None:
+        return sc
+    return sc._replace(fair_mean_diff=sc.fair_mean_diff[0], fair_mean_sq=sc.fair_mean_sq[0],
+                       fair_terms=sc.fair_terms[0])
 
 
 def split_scores_defs(pred, labels, sensitive_feat, centroids, definitions, weight_labels=None,
@@ -1135,54 +1156,5 @@ def split_scores_defs(pred, labels, sensitive_feat, centroids, definitions, weig
     weights call on the D T sources, then one mpv_split_eval_defs.  A
     definition with no active term holds NaN.  No host sync.  CPU tensors run
     ``split_scores``' torch formulas per definition."""
-    defs = [list(d) for d in definitions]
-    D = len(defs)
-    T = len(defs[0]) if defs else 0
-    if any(len(d) != T for d in defs):
-        raise ValueError("split_scores_defs needs the same number of targets in every definition "
-                         f"(got {[len(d) for d in defs]})")
-    if sensitive_feat is None or centroids is None:
-        raise ValueError("split_scores_defs needs sensitive_feat and centroids")
-    dev = pred.device
-    host = dev.type == "cpu"
-    used = (pred, labels, sensitive_feat, centroids, weight_labels)
-    if host:
-        if any(t is not None and t.device.type != "cpu" for t in used):
-            raise RuntimeError("split_scores_defs inputs must all live on one device")
-        if D == 0:
-            raise ValueError("split_scores_defs needs at least one definition")
-    else:
-        H.require_gpu(*used)
-    p = pred.detach().contiguous().float()
-    y = labels.detach().contiguous().float()
-    N, L = p.shape
-    if tuple(y.shape) != (N, L):
-        raise ValueError(f"labels {tuple(y.shape)} do not match pred {(N, L)}")
-    G = centroids.shape[0]
-    nan = torch.full((), float("nan"), dtype=torch.float64, device=dev)
-    if N == 0:  # shapes are host knowledge: no launch with an empty grid
-        return SplitScores(nan, nan.clone(), nan.expand(D).clone(), nan.expand(D).clone(),
-                           torch.full((D, T, G), float("nan"), dtype=torch.float64, device=dev),
-                           torch.zeros((3, L), dtype=torch.float64, device=dev),
-                           torch.zeros(0, dtype=torch.int32, device=dev))
-    gid, unmatched = centroid_ids(sensitive_feat, centroids)
-    wl = y if weight_labels is None else weight_labels.detach().contiguous().float()
-    if tuple(wl.shape) != (N, L):
-        raise ValueError(f"weight_labels {tuple(wl.shape)} do not match pred {(N, L)}")
-    flat = [s for d in defs for s in d]
-    if host:
-        w = _weights_host(wl, flat).reshape(D, T, N) if T else None
-        per = [_split_scores_host(p, y, None if w is None else w[d], gid, G) for d in range(D)]
-        counts, out = per[0][0], per[0][1]
-        out_defs = torch.stack([o[2:5] for _, o, _ in per])
-        terms = torch.stack([t for _, _, t in per]) if T else torch.empty((D, 0, G),
-                                                                          dtype=torch.float64)
-    else:
-        w = label_weights_batch(wl, flat)[0] if flat else None
-        order, goff = _group_layout(gid, G)
-        R = eval_slices(N, L, G, dev) if slices is None else int(slices)
-        counts, out, out_defs, terms = _split_eval_defs(p, y, w, order, goff, G, R, D, T)
-    return SplitScores(out[0], out[1], torch.where(unmatched, nan, out_defs[:, 0]),
-                       torch.where(unmatched, nan, out_defs[:, 1]),
-                       torch.where(unmatched, torch.full_like(terms, float("nan")), terms),
-                       counts, gid)
+    return _split_scores("split_scores_defs", pred, labels, sensitive_feat, centroids,
+                         list(definitions), weight_labels, slices)

@@ -240,6 +240,24 @@ class DeviceStepLR:
         return lrs
 
 
+def _warm_capture(body, warmup, prepare=None):
+    """``warmup`` eager runs of ``body()`` (at least one) on a side stream, then
+    ``prepare()`` and the capture of one more run: ``(the HIP graph, what the
+    captured run returned)``."""
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        for _ in range(max(1, warmup)):
+            body()
+    torch.cuda.current_stream().wait_stream(side)
+    graph = torch.cuda.CUDAGraph()
+    if prepare is not None:
+        prepare()
+    with torch.cuda.graph(graph):
+        out = body()
+    return graph, out
+
+
 class TrainStep:
     """The loop body of fairsoft_train.py:47-146 (penalty-free) as one call:
     ``model(label, feat)`` -> ``compute_loss`` -> ``backward`` ->
@@ -270,18 +288,32 @@ class TrainStep:
         # a plain fused Adam steps in mpv_adam_step (adam_step); others in torch
         self.native_adam = bool(native_adam) and _native_adam(optimizer)
         self.params = [p for p in model.parameters() if p.requires_grad]
-        dev = self.params[0].device
-        self.updates = torch.zeros((), dtype=torch.int64, device=dev)
-        self.found_inf = torch.zeros((), dtype=torch.float32, device=dev)
-        self._one = torch.ones((), dtype=torch.float32, device=dev)
+        self._init_state()
         self.sched = None
         if scheduler is not None:
             if not self.native_adam:
                 raise ValueError("a device StepLR needs the native Adam step (a plain fused "
                                  "torch.optim.Adam with a float lr)")
             self.sched = DeviceStepLR(scheduler, optimizer)
+
+    def _init_state(self):
+        """The step's device state, on ``self.params``' device: the applied-update
+        count, the gate's flag, and no captured graph yet."""
+        dev = self.params[0].device
+        self.updates = torch.zeros((), dtype=torch.int64, device=dev)
+        self.found_inf = torch.zeros((), dtype=torch.float32, device=dev)
+        self._one = torch.ones((), dtype=torch.float32, device=dev)
         self.graph = None
         self.label = self.feat = self.out = None
+
+    def _grads_by_dtype(self):
+        """``self.params``' gradients, one list per dtype (fp32 MLP grads, the
+        fp64 r_sqrt_sigma grad): what a multi-tensor op takes in one launch."""
+        by_dtype = {}
+        for p in self.params:
+            if p.grad is not None:
+                by_dtype.setdefault(p.grad.dtype, []).append(p.grad)
+        return by_dtype
 
     def _clip(self):
         """torch.nn.utils.clip_grad_norm_(params, max_grad_norm) (fairsoft_train.py:141)
@@ -293,10 +325,7 @@ class TrainStep:
         one copy per tensor (52 launches at the VAE's 26 fp32 gradients).  A
         clipped fp32 gradient may differ from torch's by one ulp; an unclipped
         one (coefficient 1) is untouched either way."""
-        by_dtype = {}
-        for p in self.params:
-            if p.grad is not None:
-                by_dtype.setdefault(p.grad.dtype, []).append(p.grad)
+        by_dtype = self._grads_by_dtype()
         if not by_dtype:
             return
         # torch stacks the per-tensor norms of every dtype into one promoted
@@ -340,11 +369,7 @@ class TrainStep:
         # found_inf if any gradient holds a NaN / inf; its unscale by 1.0
         # leaves every value as it is
         self.found_inf.zero_()
-        by_dtype = {}
-        for p in self.params:
-            if p.grad is not None:
-                by_dtype.setdefault(p.grad.dtype, []).append(p.grad)
-        for grads in by_dtype.values():
+        for grads in self._grads_by_dtype().values():
             torch._amp_foreach_non_finite_check_and_unscale_(grads, self.found_inf, self._one)
         if self.native_adam:
             # the update, then the step counts, `updates` and the scheduler in
@@ -399,20 +424,36 @@ class TrainStep:
         if not all(g.get("capturable") for g in self.opt.param_groups):
             raise ValueError("capture() needs torch.optim.Adam(..., fused=True, capturable=True)")
         self.label, self.feat = label.clone(), feat.clone()
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(max(1, warmup)):
-                self._body(self.label, self.feat)
-        torch.cuda.current_stream().wait_stream(side)
-        self.graph = torch.cuda.CUDAGraph()
-        self.opt.zero_grad(set_to_none=True)
-        with torch.cuda.graph(self.graph):
-            self.out = self._body(self.label, self.feat)
+        self.graph, self.out = _warm_capture(lambda: self._body(self.label, self.feat), warmup,
+                                             lambda: self.opt.zero_grad(set_to_none=True))
         return self.graph
 
 
-class CalibrationStep(TrainStep):
+class _SensInput:
+    """The batch's sensitive features as the third input of a TrainStep subclass
+    (listed before TrainStep among its bases): ``self.sens`` is the batch's own
+    tensor on an eager step and a third static buffer once captured."""
+
+    sens = None
+
+    def __call__(self, label, feat, sensitive_feat):
+        """One step (a replay once captured) on the batch."""
+        if self.graph is not None:
+            self.sens.copy_(sensitive_feat)
+        else:
+            self.sens = sensitive_feat
+        return super().__call__(label, feat)
+
+    step = __call__
+
+    def capture(self, label, feat, sensitive_feat, warmup=2):
+        """TrainStep.capture with the batch's sensitive features as a third
+        static buffer."""
+        self.sens = sensitive_feat.clone()
+        return super().capture(label, feat, warmup)
+
+
+class CalibrationStep(_SensInput, TrainStep):
     """The loop body of postprocess_threshold_one_epoch
     (fairsoft_train_postprocess.py:84-175) as one call: the frozen model's
     ``model(label, feat)`` -> ``compute_loss`` (for ``indiv_prob``) ->
@@ -456,13 +497,8 @@ class CalibrationStep(TrainStep):
         self.threshold_, self.tables, self.centroids = threshold_, tables, centroids
         self.advance_seed, self.native_adam = True, True
         self.params = [threshold_]
-        dev = threshold_.device
-        self.updates = torch.zeros((), dtype=torch.int64, device=dev)
-        self.found_inf = torch.zeros((), dtype=torch.float32, device=dev)
-        self._one = torch.ones((), dtype=torch.float32, device=dev)
+        self._init_state()
         self.sched = None if scheduler is None else DeviceStepLR(scheduler, optimizer)
-        self.graph = None
-        self.label = self.feat = self.sens = self.out = None
 
     def _body(self, label, feat):
         import mpvae
@@ -483,22 +519,6 @@ class CalibrationStep(TrainStep):
                                                          self._one)
         adam_step(self.opt, self.found_inf, self.updates, self.sched)
         return total, bce.detach(), fair.detach(), cal_prob, contributed
-
-    def __call__(self, label, feat, sensitive_feat):
-        """One step (a replay once captured) on the batch."""
-        if self.graph is not None:
-            self.sens.copy_(sensitive_feat)
-        else:
-            self.sens = sensitive_feat
-        return super().__call__(label, feat)
-
-    step = __call__
-
-    def capture(self, label, feat, sensitive_feat, warmup=2):
-        """TrainStep.capture with the batch's sensitive features as a third
-        static buffer."""
-        self.sens = sensitive_feat.clone()
-        return super().capture(label, feat, warmup)
 
 
 FairStepOut = collections.namedtuple(
@@ -531,7 +551,7 @@ class _Totals:
         self.counts.zero_()
 
 
-class FairTrainStep(TrainStep):
+class FairTrainStep(_SensInput, TrainStep):
     """The loop body of train_mpvae_softfair_one_epoch with ``penalize_unfair``
     (fairsoft_train.py:47-162) as one call: TrainStep's step with the fairness
     regulariser in the objective -- ``model(label, feat)`` -> ``compute_loss``
@@ -576,7 +596,6 @@ class FairTrainStep(TrainStep):
     def __init__(self, model, optimizer, args, tables, max_groups=None, scheduler=None):
         super().__init__(model, optimizer, args, scheduler=scheduler)
         self.tables, self.max_groups = list(tables), max_groups
-        self.sens = None
         dev = self.params[0].device
         self.totals, self.valid_totals = _Totals(dev), _Totals(dev)
 
@@ -613,22 +632,6 @@ class FairTrainStep(TrainStep):
 
     def _body(self, label, feat):
         return self._with_metrics(super()._body(label, feat), label, self.totals)
-
-    def __call__(self, label, feat, sensitive_feat):
-        """One step (a replay once captured) on the batch."""
-        if self.graph is not None:
-            self.sens.copy_(sensitive_feat)
-        else:
-            self.sens = sensitive_feat
-        return super().__call__(label, feat)
-
-    step = __call__
-
-    def capture(self, label, feat, sensitive_feat, warmup=2):
-        """TrainStep.capture with the batch's sensitive features as a third
-        static buffer."""
-        self.sens = sensitive_feat.clone()
-        return super().capture(label, feat, warmup)
 
     def validate(self, label, feat, sensitive_feat):
         """The loop body of validate_mpvae_softfair (fairsoft_train.py:234-331)
@@ -803,15 +806,8 @@ class EvalPass:
         try:
             with torch.no_grad():
                 self.label, self.feat = labels[:B].float().clone(), feats[:B].clone()
-                side = torch.cuda.Stream()
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):
-                    for _ in range(max(1, warmup)):
-                        self._batch(self.label, self.feat)
-                torch.cuda.current_stream().wait_stream(side)
-                self.graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.graph):
-                    self.out = self._batch(self.label, self.feat)
+                self.graph, self.out = _warm_capture(lambda: self._batch(self.label, self.feat),
+                                                     warmup)
         finally:
             self.model.train(was_training)
         return self.graph

@@ -1,4 +1,4 @@
-"""Time the label-similarity weights (mpvae_fair.LabelSimilarity, label_sim_kernel
+"""Time the label-similarity weights (mpvae_fair.LabelSimilarity, row_weights_kernel<LabelSims>
 in csrc/fairness.hip) and the many-definition evaluation (EvalPass(definitions=),
 mpv_split_eval_defs in csrc/evalsplit.hip) against what they replace:
 
