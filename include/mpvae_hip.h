@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MPV_ABI_VERSION 17 /* 4: device-memory Philox keys (mpv_noise_philox*_dev);
+#define MPV_ABI_VERSION 18 /* 4: device-memory Philox keys (mpv_noise_philox*_dev);
                               5: T rows padded to roundup(L, 4) floats;
                               6: mpv_linear (the VAE's Linear layers); mpv_bwd_args
                                  dR64 and kl;
@@ -64,7 +64,10 @@ extern "C" {
                              17: mpv_label_sim_weights (row weights from a
                                  closed-form label similarity, no table),
                                  mpv_split_eval_defs (a split scored under D
-                                 weight definitions in one pass) */
+                                 weight definitions in one pass)
+                             18: mpv_gather_batch (a batch gathered from a
+                                 device-resident split at a device cursor);
+                                 MPV_EL_U8 */
 
 enum mpv_status { MPV_OK = 0, MPV_EINVAL = 1, MPV_ELAUNCH = 2 };
 enum mpv_dtype { MPV_F32 = 0, MPV_F64 = 1 };
@@ -477,7 +480,8 @@ int mpv_adam_finish(const mpv_adam_finish_args* args, void* stream);
  * (the merge passes), curve_pass, curve_agg, metric_sweep (every launch of
  * mpv_threshold_sweep), calib_fwd, calib_tables, calib_bwd, probit_predict,
  * predict_final (the two launches of mpv_probit_predict), split_eval, split_final
- * (the two launches of mpv_split_eval and of mpv_split_eval_defs).  Query synchronises the recorded events. */
+ * (the two launches of mpv_split_eval and of mpv_split_eval_defs), gather_batch (the
+ * gather of mpv_gather_batch and its cursor launch).  Query synchronises the recorded events. */
 int mpv_timing_enable(int on);
 int mpv_timing_reset(void);
 int mpv_timing_query(const char* kernel, int64_t* launches, double* total_ms);
@@ -568,7 +572,8 @@ int mpv_label_sim_weights(const float* y, int64_t B, int64_t L, const mpv_label_
  * Supported: 1 <= B <= MPV_GROUP_MAX_B, 1 <= n <= MPV_GROUP_MAX_N,
  * 1 <= G <= MPV_GROUP_MAX_B (G may exceed B: the slots past the batch's groups
  * stay empty); anything else is MPV_EINVAL and launches nothing. */
-enum mpv_elem { MPV_EL_F32 = 0, MPV_EL_F64 = 1, MPV_EL_I32 = 2, MPV_EL_I64 = 3 };
+enum mpv_elem { MPV_EL_F32 = 0, MPV_EL_F64 = 1, MPV_EL_I32 = 2, MPV_EL_I64 = 3,
+                MPV_EL_U8 = 4 /* mpv_gather_batch only */ };
 #define MPV_GROUP_MAX_B 4096
 #define MPV_GROUP_MAX_N 64
 int mpv_group_rows(const void* x, int x_elem, int64_t B, int64_t n, int64_t G, int32_t* gid,
@@ -755,6 +760,49 @@ int mpv_split_eval(const mpv_split_eval_args* args, void* workspace, size_t work
  * mpv_split_eval_workspace_bytes(N, L, D * T, G, R); 1 <= D, D * T <= 2^20. */
 int mpv_split_eval_defs(const mpv_split_eval_args* args, int64_t D, double* out_defs,
                         void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- The batch feed of an epoch (fairsoft_train.py:48-56, :235-243, :266-267;
+ * gather.hip) ------------------------------------------------------------------
+ * The reference builds each batch on the host: data.X[idx] (a numpy gather),
+ * .float() and a host-to-device copy, for the features, the labels and the
+ * sensitive columns.  Here the split's matrices stay in device memory and one
+ * call gathers a batch of up to MPV_GATHER_MAX_SOURCES of them: with
+ * p = pos ? *pos : start, for r in [0, B) and every source k
+ *   dst[k][r, :] = cast(src[k][idx[p + r], :])       (idx NULL: row p + r)
+ * where cast is static_cast<float> when dst_elem[k] is MPV_EL_F32 (torch's
+ * .float(): round to nearest even from fp64 and 64-bit integers) and a raw
+ * copy when dst_elem[k] == src_elem[k].  All matrices are row-major and dense
+ * (row pitch = cols elements).  A row with p + r outside [0, n_idx) or an index
+ * outside [0, n_rows) reads nothing out of range: it is NaN in a floating-point
+ * destination, zero bytes in an integer one, and *bad (one byte) is set to 1;
+ * the call never clears *bad.  With advance = 1 (needs pos) *pos is p + B
+ * after the call, moved by a one-thread launch behind the gather on the same
+ * stream: every row has read p, and no workgroup waits for another.  p is read
+ * on the device, so the call can be a node of a captured graph that walks an
+ * epoch's order replay by replay.  A raw copy whose bases and row pitches are
+ * 16-B aligned moves 16 bytes per lane, anything else one element per lane;
+ * plain stores.  n_sources outside 1..4, B < 1, cols < 1, a NULL src / dst /
+ * bad, an unknown src_elem, a dst_elem that is neither MPV_EL_F32 nor the
+ * source's, or advance without pos is MPV_EINVAL and launches nothing. */
+#define MPV_GATHER_MAX_SOURCES 4
+typedef struct mpv_gather_args {
+  const void* src[MPV_GATHER_MAX_SOURCES];  /* (n_rows, cols[k]) of src_elem[k] */
+  int32_t src_elem[MPV_GATHER_MAX_SOURCES]; /* mpv_elem */
+  int64_t cols[MPV_GATHER_MAX_SOURCES];
+  void* dst[MPV_GATHER_MAX_SOURCES];        /* (B, cols[k]) of dst_elem[k] */
+  int32_t dst_elem[MPV_GATHER_MAX_SOURCES];
+  int32_t n_sources;
+  int64_t n_rows;     /* rows of every source */
+  const int64_t* idx; /* n_idx row indices in device memory, or NULL: the identity */
+  int64_t n_idx;
+  int64_t B;
+  int64_t start;      /* the batch's first position when pos is NULL */
+  int64_t* pos;       /* NULL, or the position in device memory (written with advance only) */
+  int32_t advance;    /* 0 / 1 */
+  uint8_t* bad;       /* one byte in device memory */
+} mpv_gather_args;
+
+int mpv_gather_batch(const mpv_gather_args* args, void* stream);
 
 #ifdef __cplusplus
 }

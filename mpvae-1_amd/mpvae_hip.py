@@ -13,7 +13,7 @@ import torch  # noqa: F401  (must precede the .so load: one HIP runtime per proc
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MPVAE_HIP_LIB", os.path.join(HERE, "libmpvae_hip.so"))
 
-ABI_VERSION = 17
+ABI_VERSION = 18
 F32, F64 = 0, 1
 G_TOTAL, G_NLL, G_NLL_X, G_C, G_C_X, G_KL = range(6)
 
@@ -109,7 +109,7 @@ SIM_INDICATION, SIM_CONSTANT, SIM_JACCARD, SIM_HAMMING = range(4)  # mpv_sim_kin
 LABEL_SIMS_PER_LAUNCH = 8  # MPV_LABEL_SIMS_PER_LAUNCH
 FAIR_L1, FAIR_L2 = 1, 2
 LABEL_TABLES_PER_LAUNCH = 8  # MPV_LABEL_TABLES_PER_LAUNCH
-EL_F32, EL_F64, EL_I32, EL_I64 = range(4)  # mpv_elem
+EL_F32, EL_F64, EL_I32, EL_I64, EL_U8 = range(5)  # mpv_elem (EL_U8: mpv_gather_batch only)
 GROUP_MAX_B, GROUP_MAX_N = 4096, 64  # mpv_group_rows' supported range
 EINVAL = 1
 
@@ -187,6 +187,19 @@ class SplitEvalArgs(ctypes.Structure):
                 ("N", ctypes.c_int64), ("L", ctypes.c_int64), ("T", ctypes.c_int64),
                 ("G", ctypes.c_int64), ("R", ctypes.c_int64), ("counts", vp), ("terms", vp),
                 ("out", vp)]
+
+
+GATHER_MAX_SOURCES = 4
+
+
+class GatherArgs(ctypes.Structure):
+    """mpv_gather_args: one batch gathered from a device-resident split (gather.hip)."""
+    _fields_ = [("src", vp * GATHER_MAX_SOURCES), ("src_elem", ctypes.c_int32 * GATHER_MAX_SOURCES),
+                ("cols", ctypes.c_int64 * GATHER_MAX_SOURCES), ("dst", vp * GATHER_MAX_SOURCES),
+                ("dst_elem", ctypes.c_int32 * GATHER_MAX_SOURCES), ("n_sources", ctypes.c_int32),
+                ("n_rows", ctypes.c_int64), ("idx", vp), ("n_idx", ctypes.c_int64),
+                ("B", ctypes.c_int64), ("start", ctypes.c_int64), ("pos", vp),
+                ("advance", ctypes.c_int32), ("bad", vp)]
 
 
 # name -> (restype, argtypes); exactly the symbols of include/mpvae_hip.h
@@ -268,6 +281,7 @@ SIGNATURES = {
     "mpv_split_eval": (ctypes.c_int, [ctypes.POINTER(SplitEvalArgs), vp, ctypes.c_size_t, vp]),
     "mpv_split_eval_defs": (ctypes.c_int, [ctypes.POINTER(SplitEvalArgs), ctypes.c_int64, vp, vp,
                                            ctypes.c_size_t, vp]),
+    "mpv_gather_batch": (ctypes.c_int, [ctypes.POINTER(GatherArgs), vp]),
 }
 
 _lib = None
@@ -332,7 +346,7 @@ KERNELS = ["noise_philox", "split", "probit_fwd", "fwd_combine", "finalize", "bw
            "kl_bwd", "label_weights", "label_sim", "group_rows", "fair_fwd", "fair_bwd", "metrics", "linear", "adam",
            "adam_finish", "curve_keys", "curve_sort", "curve_merge", "curve_pass", "curve_agg",
            "metric_sweep", "calib_fwd", "calib_tables", "calib_bwd", "probit_predict",
-           "predict_final", "split_eval", "split_final"]
+           "predict_final", "split_eval", "split_final", "gather_batch"]
 
 
 def kernel_times():

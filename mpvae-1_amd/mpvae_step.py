@@ -15,6 +15,13 @@ fairsoft_train.py:154-162).  Each sync drains the stream.  Here:
 
 Both are torch glue around the loop, not kernels of the hot path: they run on
 whatever device the tensors live on.
+
+The loop bodies themselves are one call each (``TrainStep``, ``FairTrainStep``,
+``CalibrationStep``, ``EvalPass``), and so is the feeding of their batches:
+``DeviceSplit`` keeps a split on the device and ``run_epoch`` /
+``capture_epoch`` / ``validate_epoch`` / ``run_split`` gather every batch there
+(mpv_gather_batch, csrc/gather.hip) instead of the reference's per-batch
+``torch.from_numpy(data[idx]).float().to(device)``.
 """
 import collections
 import copy
@@ -258,6 +265,221 @@ def _warm_capture(body, warmup, prepare=None):
     return graph, out
 
 
+_SPLIT_ELEMS = {torch.float32: 0, torch.float64: 1, torch.int32: 2, torch.int64: 3,
+                torch.uint8: 4}  # dtype -> mpv_elem
+
+
+class DeviceSplit:
+    """A dataset split resident on one device, and the batches gathered from
+    it there: what the reference builds per batch on the host as
+    ``torch.from_numpy(data.input_feat[idx]).float().to(device)`` for the
+    features, the labels and the sensitive columns (fairsoft_train.py:48-56,
+    :235-243, :266-267).
+
+    ``labels`` (N, L), ``feats`` (N, F) and ``sensitive_feat`` (N, n, optional)
+    are numpy arrays or tensors; each is held contiguous in its own dtype
+    (fp32, fp64, int32, int64 or uint8, so a large 0/1 label matrix can stay
+    uint8) on ``device`` (default: where ``feats`` already lives, the CPU for a
+    numpy array).
+
+    ``gather(order, start, B)`` returns rows ``order[start : start + B]`` as
+    ``(label fp32, feat fp32, sens in its own dtype)`` -- the values ``.float()``
+    gives.  On a GPU this is one ``mpv_gather_batch`` launch (csrc/gather.hip);
+    on the CPU, torch indexing with the same semantics.  The dispatch is by the
+    split's device; there is no fallback from one to the other.  A position
+    outside the order or an index outside the split reads nothing: the row is
+    NaN (fp32 outputs; a floating-point ``sens``) or 0 (an integer ``sens``) and
+    the device flag ``bad`` is set.  ``check()`` (one host sync) raises if it
+    is.  A numpy ``order`` is range-checked on the host before it is uploaded;
+    the flag is the backstop for an order that is already a tensor.
+
+    The split also owns the state an epoch loop walks (TrainStep.run_epoch):
+    ``order`` (int64, capacity N; the rows past the current order hold -1),
+    ``n_order`` and the device ``cursor``.  Their addresses never change, so a
+    captured epoch graph reads them on every replay."""
+
+    def __init__(self, labels, feats, sensitive_feat=None, device=None):
+        if device is None:
+            device = feats.device if isinstance(feats, torch.Tensor) else "cpu"
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.labels = self._hold(labels, "labels")
+        self.feats = self._hold(feats, "feats")
+        self.sens = None if sensitive_feat is None else self._hold(sensitive_feat,
+                                                                   "sensitive_feat")
+        self.n_rows = int(self.labels.shape[0])
+        held = [t for t in (self.labels, self.feats, self.sens) if t is not None]
+        if self.n_rows < 1 or any(t.shape[0] != self.n_rows or t.shape[1] < 1 for t in held):
+            raise ValueError("DeviceSplit needs labels, feats and sensitive_feat with the same "
+                             "number (>= 1) of rows and at least one column each")
+        self.order = torch.arange(self.n_rows, dtype=torch.int64, device=self.device)
+        self.n_order = self.n_rows
+        self.cursor = torch.zeros((), dtype=torch.int64, device=self.device)
+        self.bad = torch.zeros((), dtype=torch.uint8, device=self.device)
+
+    def _hold(self, x, name):
+        t = x if isinstance(x, torch.Tensor) else torch.from_numpy(_np().ascontiguousarray(x))
+        if t.dtype not in _SPLIT_ELEMS:
+            raise ValueError(f"DeviceSplit holds fp32, fp64, int32, int64 or uint8 ({name} is "
+                             f"{t.dtype})")
+        if t.dim() != 2:
+            raise ValueError(f"DeviceSplit: {name} must be a 2-D matrix (got {tuple(t.shape)})")
+        return t.detach().to(self.device).contiguous()
+
+    # ----------------------------------------------------------------- order
+    def _index_tensor(self, order):
+        """``order`` as an int64 tensor on the split's device.  A numpy order is
+        range-checked on the host first; a tensor is taken as it is."""
+        if isinstance(order, torch.Tensor):
+            if order.dim() != 1 or order.dtype.is_floating_point or order.dtype == torch.bool:
+                raise ValueError("order must be a 1-D integer tensor")
+            return order.detach().to(device=self.device, dtype=torch.int64).contiguous()
+        np = _np()
+        arr = np.asarray(order)
+        if arr.ndim != 1 or arr.dtype.kind not in "iu":
+            raise ValueError("order must be a 1-D array of integer row indices")
+        if arr.size and (int(arr.min()) < 0 or int(arr.max()) >= self.n_rows):
+            raise IndexError(f"order holds a row index outside [0, {self.n_rows}) "
+                             f"(min {int(arr.min())}, max {int(arr.max())})")
+        src = torch.from_numpy(np.ascontiguousarray(arr, dtype=np.int64))
+        if self.device.type != "cuda":
+            return src.clone()
+        return src.pin_memory().to(self.device, non_blocking=True)
+
+    def set_order(self, order):
+        """Upload an epoch's order (``data.train_idx`` after the caller's
+        ``np.random.shuffle``; None: the identity) into the static order buffer
+        and put the cursor at 0; returns its length.  No host sync."""
+        if order is None:
+            idx = torch.arange(self.n_rows, dtype=torch.int64, device=self.device)
+        else:
+            idx = self._index_tensor(order)
+        n = int(idx.shape[0])
+        if n > self.n_rows:
+            raise ValueError(f"an epoch's order holds at most the split's {self.n_rows} rows "
+                             f"(got {n})")
+        self.order[:n].copy_(idx)
+        if n < self.n_rows:
+            self.order[n:].fill_(-1)
+        self.n_order = n
+        self.cursor.zero_()
+        return n
+
+    # ---------------------------------------------------------------- gather
+    def _sources(self, sens):
+        src = [(self.labels, torch.float32), (self.feats, torch.float32)]
+        if sens:
+            if self.sens is None:
+                raise ValueError("this DeviceSplit holds no sensitive_feat")
+            src.append((self.sens, self.sens.dtype))
+        return src
+
+    def _gather(self, idx, n_idx, B, start=0, pos=None, advance=False, out=None, sens=True):
+        """Rows ``idx[p : p + B]`` (``idx`` None: rows p .. p + B) of every source,
+        p = ``pos`` (a device int64 scalar) or ``start``; with ``advance`` the
+        cursor ``pos`` moves by B afterwards."""
+        B = int(B)
+        if B < 1:
+            raise ValueError(f"a batch needs at least one row (got B = {B})")
+        if advance and pos is None:
+            raise ValueError("advance needs a device cursor")
+        src = self._sources(sens)
+        if out is None:
+            out = [torch.empty((B, t.shape[1]), dtype=dt, device=self.device) for t, dt in src]
+        out = list(out)
+        if len(out) != len(src) or any(
+                o.shape != (B, t.shape[1]) or o.dtype != dt or o.device != self.device
+                or not o.is_contiguous() for o, (t, dt) in zip(out, src)):
+            raise ValueError("out must hold one contiguous (B, cols) tensor per source, on the "
+                             "split's device: label fp32, feat fp32, sens in its own dtype")
+        if self.device.type == "cuda":
+            import mpvae_hip as H
+            a = H.GatherArgs(n_sources=len(src), n_rows=self.n_rows, idx=H.ptr(idx),
+                             n_idx=int(n_idx), B=B, start=int(start), pos=H.ptr(pos),
+                             advance=int(bool(advance)), bad=H.ptr(self.bad))
+            for k, ((t, dt), o) in enumerate(zip(src, out)):
+                a.src[k], a.src_elem[k], a.cols[k] = t.data_ptr(), _SPLIT_ELEMS[t.dtype], t.shape[1]
+                a.dst[k], a.dst_elem[k] = o.data_ptr(), _SPLIT_ELEMS[dt]
+            H.check(H.load_library().mpv_gather_batch(ctypes.byref(a), H.stream_of(self.device)),
+                    "mpv_gather_batch")
+        else:
+            self._gather_cpu(src, out, idx, int(n_idx), B, int(start), pos, advance)
+        return tuple(out) if sens else (out[0], out[1], None)
+
+    def _gather_cpu(self, src, out, idx, n_idx, B, start, pos, advance):
+        """mpv_gather_batch's semantics on CPU tensors, in torch."""
+        p = int(pos) if pos is not None else start
+        r = torch.arange(B, dtype=torch.int64)
+        ok = (-r <= p) & (n_idx - r > p)  # p + r in [0, n_idx), before the sum is formed
+        q = torch.where(ok, r + (p if -B <= p <= n_idx else 0), torch.zeros_like(r))
+        rows = q
+        if idx is not None and n_idx > 0:
+            rows = idx[q.clamp(0, n_idx - 1)]
+        ok &= (rows >= 0) & (rows < self.n_rows)
+        rows = rows.clamp(0, self.n_rows - 1)
+        for (t, dt), o in zip(src, out):
+            v = t[rows].to(dt)
+            v[~ok] = float("nan") if dt.is_floating_point else 0
+            o.copy_(v)
+        if not bool(ok.all()):
+            self.bad.fill_(1)
+        if advance:
+            pos += B
+
+    def gather(self, order, start, B, out=None):
+        """``(label fp32, feat fp32, sens)`` of rows ``order[start : start + B]``
+        (``order`` None: rows ``start .. start + B``); ``sens`` is None when the
+        split holds no sensitive_feat.  ``start`` is an int, or a 0-d int64
+        tensor on the split's device (read there, no host sync).  ``out``: the
+        tensors to write, as returned by an earlier call with the same B."""
+        idx = None if order is None else self._index_tensor(order)
+        n_idx = self.n_rows if idx is None else int(idx.shape[0])
+        pos = start if isinstance(start, torch.Tensor) else None
+        if pos is not None and (pos.dtype != torch.int64 or pos.numel() != 1
+                                or pos.device != self.device):
+            raise ValueError("a tensor start must be one int64 on the split's device")
+        return self._gather(idx, n_idx, B, 0 if pos is not None else int(start), pos, False,
+                            out, self.sens is not None)
+
+    def next_batch(self, B, advance=True, out=None, sens=True):
+        """The B rows of the current order at the device cursor, which then moves
+        past them (``advance``): the feed of one step of an epoch."""
+        # the bound is the buffer's capacity, not n_order, so that a captured
+        # launch stays right for a later, longer order; the rows past the
+        # current order hold -1 and are flagged like any other bad index
+        return self._gather(self.order, self.n_rows, B, 0, self.cursor, advance, out, sens)
+
+    def check(self):
+        """One host sync: raises IndexError if a gather met a position outside its
+        order or a row index outside the split since the last check (the rows it
+        wrote are NaN / 0), and clears the flag."""
+        if int(self.bad):
+            self.bad.zero_()
+            raise IndexError("DeviceSplit: a gathered batch held a position past the end of its "
+                             f"order or a row index outside [0, {self.n_rows}) -- most likely "
+                             "`order` holds an out-of-range index; those rows were written as "
+                             "NaN / 0")
+
+
+def epoch_batches(n, batch_size):
+    """The reference's batches over n rows (fairsoft_train.py:48-56):
+    ``range(n // B + 1)`` over ``[i B, min((i + 1) B, n))`` without the empty last
+    one (n a multiple of B) -- ``(full batches, rows of the ragged last batch)``."""
+    B = int(batch_size)
+    if B < 1:
+        raise ValueError(f"batch_size must be >= 1 (got {batch_size})")
+    return int(n) // B, int(n) % B
+
+
+def _np():
+    import numpy
+    return numpy
+
+
+_EpochGraph = collections.namedtuple("_EpochGraph", ["graph", "split", "B", "bufs", "out"])
+
+
 class TrainStep:
     """The loop body of fairsoft_train.py:47-146 (penalty-free) as one call:
     ``model(label, feat)`` -> ``compute_loss`` -> ``backward`` ->
@@ -305,6 +527,7 @@ class TrainStep:
         self._one = torch.ones((), dtype=torch.float32, device=dev)
         self.graph = None
         self.label = self.feat = self.out = None
+        self._epoch = None  # capture_epoch's graph and static buffers
 
     def _grads_by_dtype(self):
         """``self.params``' gradients, one list per dtype (fp32 MLP grads, the
@@ -399,6 +622,7 @@ class TrainStep:
         if self.sched is None:
             return None
         lrs, self.sched = self.sched.release(), None
+        self._epoch = None
         if self.graph is not None:
             self.graph = None
             self.label = self.feat = self.out = None
@@ -428,6 +652,91 @@ class TrainStep:
                                              lambda: self.opt.zero_grad(set_to_none=True))
         return self.graph
 
+    # ---------------------------------------------------------------- epochs
+    _epoch_sens = False  # the step reads the batch's sensitive features (_SensInput)
+
+    def _epoch_body(self, label, feat, sens):
+        """``_body`` on a gathered batch."""
+        return self._body(label, feat)
+
+    def _epoch_step(self, split, B):
+        """Gather the next B rows of the split's order at its cursor, then the step."""
+        return self._epoch_body(*split.next_batch(B, sens=self._epoch_sens))
+
+    def run_epoch(self, split, order, batch_size):
+        """One epoch of the reference's loop (fairsoft_train.py:47-56) over a
+        ``DeviceSplit``, fed on the device: ``order`` (the caller's shuffled
+        ``data.train_idx``, numpy or tensor; None: every row in turn) is
+        uploaded once, the cursor is put at 0, and every batch of the
+        reference's -- ``range(N // B + 1)`` over ``[i B, min((i + 1) B, N))``, the
+        empty last one skipped -- is gathered at the cursor by one
+        ``mpv_gather_batch`` launch and stepped.  A full batch is a replay of the
+        epoch graph when ``capture_epoch`` recorded one for this split and batch
+        size (nothing else is enqueued between two replays), and the eager
+        gather and step otherwise; the ragged last batch always runs eagerly,
+        through the same kernel.  Afterwards the cursor is at ``N - N % B``.
+        Returns the number of steps; no host sync (``read_totals()`` /
+        ``split.check()`` are the caller's)."""
+        B = int(batch_size)
+        if B < 1:
+            raise ValueError(f"batch_size must be >= 1 (got {batch_size})")
+        full, tail = epoch_batches(split.set_order(order), B)
+        if self.sched is not None:
+            self.sched.adopt_host_lr()
+        ep = self._epoch
+        if ep is not None and ep.split is split and ep.B == B:
+            for _ in range(full):
+                ep.graph.replay()
+        else:
+            for _ in range(full):
+                self._epoch_step(split, B)
+        if tail:
+            self._epoch_body(*split.next_batch(tail, advance=False, sens=self._epoch_sens))
+        return full + (1 if tail else 0)
+
+    def capture_epoch(self, split, batch_size, warmup=2):
+        """Record one full-batch step of ``run_epoch`` in a HIP graph: the gather
+        (it reads the split's static order buffer at the device cursor and moves
+        the cursor on) followed by the step on the gathered static buffers.
+        ``warmup`` eager steps on a side stream first, each on the first
+        ``batch_size`` rows of the split's current order (they update the model,
+        as capture()'s do); the cursor is back at 0 afterwards.  Needs what
+        capture() needs -- ``args.mpvae_noise = "philox"``, a device-tensor
+        ``args.mpvae_seed`` and ``torch.optim.Adam(..., fused=True,
+        capturable=True)`` -- and a split on the model's GPU whose current order
+        holds a full batch.  ``capture()`` and ``__call__`` keep their own graph
+        and buffers."""
+        B = int(batch_size)
+        if not all(g.get("capturable") for g in self.opt.param_groups):
+            raise ValueError("capture_epoch() needs torch.optim.Adam(..., fused=True, "
+                             "capturable=True)")
+        if getattr(self.args, "mpvae_noise", "torch_cpu") != "philox" or not isinstance(
+                getattr(self.args, "mpvae_seed", None), torch.Tensor):
+            raise ValueError("capture_epoch() needs args.mpvae_noise = 'philox' and a one-element "
+                             "int64 device tensor as args.mpvae_seed")
+        if split.device.type != "cuda" or split.device != self.params[0].device:
+            raise ValueError("capture_epoch() needs a DeviceSplit on the model's GPU")
+        if B < 1 or split.n_order < B:
+            raise ValueError(f"capture_epoch() needs a full batch of {B} rows in the split's "
+                             f"current order (it holds {split.n_order})")
+        bufs = [torch.empty((B, t.shape[1]), dtype=dt, device=split.device)
+                for t, dt in split._sources(self._epoch_sens)]
+        warming = [True]
+
+        def body():
+            if warming[0]:
+                split.cursor.zero_()
+            return self._epoch_body(*split.next_batch(B, out=bufs, sens=self._epoch_sens))
+
+        def prepare():
+            warming[0] = False
+            self.opt.zero_grad(set_to_none=True)
+
+        graph, out = _warm_capture(body, warmup, prepare)
+        split.cursor.zero_()
+        self._epoch = _EpochGraph(graph, split, B, bufs, out)
+        return graph
+
 
 class _SensInput:
     """The batch's sensitive features as the third input of a TrainStep subclass
@@ -451,6 +760,17 @@ class _SensInput:
         static buffer."""
         self.sens = sensitive_feat.clone()
         return super().capture(label, feat, warmup)
+
+    _epoch_sens = True  # run_epoch gathers the sensitive features as a third source
+
+    def _epoch_body(self, label, feat, sens):
+        """``_body`` with the gathered sensitive features; ``self.sens`` (the
+        static buffer of a captured ``step``) is put back afterwards."""
+        kept, self.sens = self.sens, sens
+        try:
+            return self._body(label, feat)
+        finally:
+            self.sens = kept
 
 
 class CalibrationStep(_SensInput, TrainStep):
@@ -652,6 +972,22 @@ class FairTrainStep(_SensInput, TrainStep):
             self.sens = sens
             self.model.train(was_training)
 
+    def validate_epoch(self, split, order, batch_size):
+        """validate_mpvae_softfair's loop (fairsoft_train.py:233-331) over a
+        ``DeviceSplit``: ``validate()`` on every batch of ``order``
+        (``data.valid_idx``; run_epoch's batch rule), each gathered on the device
+        at the split's cursor; eager.  The sums go to ``valid_totals``; returns
+        the number of batches, no host sync."""
+        B = int(batch_size)
+        if B < 1:
+            raise ValueError(f"batch_size must be >= 1 (got {batch_size})")
+        full, tail = epoch_batches(split.set_order(order), B)
+        for _ in range(full):
+            self.validate(*split.next_batch(B))
+        if tail:
+            self.validate(*split.next_batch(tail, advance=False))
+        return full + (1 if tail else 0)
+
     def read_totals(self, reset=True):
         """The running sums as Python numbers, with one host sync: the SUM_KEYS
         sums (divide by ``steps`` for the reference's running_postfix),
@@ -786,6 +1122,19 @@ class EvalPass:
         finally:
             self.model.train(was_training)
         return EvalOut(buf, scores)
+
+    def run_split(self, split, order=None, weight_labels=None):
+        """``run`` on the rows ``order`` of a ``DeviceSplit`` (None: all of them, in
+        place): one ``mpv_gather_batch`` launch collects ``labels[order]`` (as
+        fp32), ``feats[order]`` and ``sensitive_feat[order]`` on the device -- what
+        a caller of ``run`` materialises on the host for a subset -- and ``run``
+        takes them.  ``weight_labels`` is ``run``'s, row-aligned with ``order``."""
+        if order is None and split.feats.dtype == torch.float32:
+            labels, feats, sens = split.labels, split.feats, split.sens
+        else:
+            n = split.n_rows if order is None else len(order)
+            labels, feats, sens = split.gather(order, 0, n)
+        return self.run(labels, feats, sens, weight_labels)
 
     def capture(self, labels, feats, warmup=2):
         """Record the body of a full batch in a HIP graph on static copies of the
