@@ -23,6 +23,19 @@ inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 // Shape sanity shared by forward and backward.
 int check_shape(const mpv_shape* s);
 
+// out[i] = sum over k < nslab of in[k * n + i], the slabs in order (util.hip);
+// out_dtype MPV_F32 or MPV_F64.  The pair is two such sums in one launch, each
+// with the bits of a launch of its own.
+int launch_sum_slabs(const float* in, int64_t nslab, int64_t n, void* out, int out_dtype,
+                     hipStream_t s);
+// Whether that sum takes the split layout (16 strided slab groups per output
+// element, added in order) rather than slab by slab: too few columns to hide
+// the slab chain.  predict_final sums in the same order.
+inline bool slab_sum_is_split(int64_t nslab, int64_t n) { return nslab >= 64 && n <= 256 * 256; }
+int launch_sum_slabs_pair(const float* in0, int64_t nslab0, int64_t n0, void* out0,
+                          int out0_dtype, const float* in1, int64_t nslab1, int64_t n1,
+                          void* out1, int out1_dtype, hipStream_t s);
+
 // Brackets one kernel launch with HIP events when mpv_timing_enable(1) is on
 // (no cost otherwise beyond one branch).
 class TimedLaunch {

@@ -26,6 +26,16 @@ constexpr float kKlWeight = 1.1f;
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
+// An MPV_F32 / MPV_F64 tag as a type: calls f(float{}) or f(double{}), so a
+// generic lambda reads the element type off its argument (host and device).
+template <typename F>
+__host__ __device__ __forceinline__ void with_dtype(int dtype, F&& f) {
+  if (dtype == MPV_F64)
+    f(double{});
+  else
+    f(float{});
+}
+
 // Hardware transcendentals (v_exp_f32 / v_log_f32 are base 2).
 MPV_DEV float fast_log(float x) { return __builtin_amdgcn_logf(x) * 0.6931471805599453f; }
 MPV_DEV float fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }

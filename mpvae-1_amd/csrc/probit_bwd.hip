@@ -36,12 +36,6 @@
 
 namespace mpv {
 
-int launch_sum_slabs(const float* in, int64_t nslab, int64_t n, void* out, int out_dtype,
-                     hipStream_t s);
-int launch_sum_slabs_pair(const float* in0, int64_t nslab0, int64_t n0, void* out0,
-                          int out0_dtype, const float* in1, int64_t nslab1, int64_t n1,
-                          void* out1, int out1_dtype, hipStream_t s);
-
 // Upper bounds used for the G scale (3xf16): for E = Phi(u)(1-1e-6)+0.5e-6,
 // sup_u phi(u) |y/E - (1-y)/(1-E)| < 4.5 (inverse Mills ratio capped by the
 // 0.5e-6 floor), phi(u) e^{-5E} <= 0.4, phi(u) e^{5E} <= 0.4 e^5 < 60.  Only the

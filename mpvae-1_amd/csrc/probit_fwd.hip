@@ -52,9 +52,6 @@
 
 namespace mpv {
 
-int launch_sum_slabs(const float* in, int64_t nslab, int64_t n, void* out, int out_dtype,
-                     hipStream_t s);
-
 struct FwdParams {
   const float* y;
   const float* fe;
@@ -1436,8 +1433,8 @@ __global__ __launch_bounds__(kFwd16Threads, 1) void probit_fwd16_kernel(FwdParam
 
 // After the prediction tiles (mpv_probit_predict): colsum (B, L) = the sum of
 // the nSc column partials (part != NULL) in the order the full forward sums
-// the same shape's -- chunk by chunk (fwd_combine's fold and sum_slabs_kernel),
-// or, `split`, sum_slabs_split_kernel's 16 strided groups added in order --
+// the same shape's -- chunk by chunk (fwd_combine's fold and slab_sum_plain),
+// or, `split`, slab_sum_split's 16 strided groups added in order --
 // indiv_prob = colsum / S_total (write_indiv's division), and the device
 // Philox key's advance (as finalize_kernel).
 __global__ __launch_bounds__(256) void predict_final_kernel(const float* __restrict__ part, int nSc,
@@ -1896,7 +1893,7 @@ static int run_predict(const mpv_shape* shape, const mpv_predict_args* a, void* 
   // The order of the full forward's sum of the same shape's partials: its
   // buffer is (2, B, L), so launch_sum_slabs' split rule sees n = 2 B L.
   const int64_t n = shape->B * shape->L;
-  const int split = pl.nSc > kCombineFoldSlabs && 2 * n <= 256 * 256;
+  const int split = pl.nSc > kCombineFoldSlabs && slab_sum_is_split(pl.nSc, 2 * n);
   int64_t nb = cdiv(n, 256);
   if (nb > 2048) nb = 2048;
   MPV_LAUNCH("predict_final", predict_final_kernel, dim3((unsigned)nb), dim3(256), 0, st,

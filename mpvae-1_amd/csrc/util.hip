@@ -137,109 +137,97 @@ __global__ void convert_kernel(const S* __restrict__ src, D* __restrict__ dst, i
     dst[i] = (D)src[i];
 }
 
-// out[i] = sum_k in[k*n + i], k < nslab (fixed order -> deterministic).
-template <typename D>
-__global__ void sum_slabs_kernel(const float* __restrict__ in, int64_t nslab, int64_t n,
-                                 D* __restrict__ out) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    float acc = 0.0f;
-    // fixed summation order (deterministic); unrolled so that the loads of
-    // several slabs are in flight together
-#pragma unroll 8
-    for (int64_t k = 0; k < nslab; ++k) acc += in[k * n + i];
-    out[i] = (D)acc;
-  }
+// ---------------------------------------------------------------- slab sums
+// out[i] = sum_k in[k*n + i], k < nslab, the slabs in order (deterministic),
+// in one of three layouts that slab_problem chooses; per output element each
+// adds the same values in the same order.
+struct SlabSum {
+  const float* in;
+  int64_t nslab, n;
+  void* out;
+  int out_dtype;  // MPV_F32 / MPV_F64
+  int split;      // few columns, many slabs: 64 columns per workgroup
+  int vec;        // 4 consecutive elements per thread (16-B loads): n % 4 == 0, aligned
+  int64_t blocks;
+};
+
+MPV_DEV void slab_store(const SlabSum& q, int64_t i, float v) {
+  with_dtype(q.out_dtype, [&](auto t) {
+    typedef decltype(t) D;
+    reinterpret_cast<D*>(q.out)[i] = (D)v;
+  });
 }
 
 // Few columns over many slabs (small L x z, or the column partials): 16 waves
 // per workgroup split the slabs (wave g sums slabs g, g+16, ..., one coalesced
 // 256-B row each), then a fixed-order sum of the 16 partials through LDS: the
 // serial chain per lane is nslab/16 loads instead of nslab.
-template <typename D>
-__global__ __launch_bounds__(1024) void sum_slabs_split_kernel(const float* __restrict__ in,
-                                                               int64_t nslab, int64_t n,
-                                                               D* __restrict__ out) {
-  __shared__ float part[16][65];
+MPV_DEV void slab_sum_split(const SlabSum& q, int64_t blk, float (*part)[65]) {
   const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
-  const int64_t i = (int64_t)blockIdx.x * 64 + lane;
+  const int64_t i = blk * 64 + lane;
   float acc = 0.0f;
-  if (i < n) {
+  if (i < q.n) {
 #pragma unroll 4
-    for (int64_t k = g; k < nslab; k += 16) acc += in[k * n + i];
+    for (int64_t k = g; k < q.nslab; k += 16) acc += q.in[k * q.n + i];
   }
   part[g][lane] = acc;
   __syncthreads();
-  if (g == 0 && i < n) {
+  if (g == 0 && i < q.n) {
     float t = part[0][lane];
 #pragma unroll
     for (int j = 1; j < 16; ++j) t += part[j][lane];
-    out[i] = (D)t;
+    slab_store(q, i, t);
   }
 }
 
-// Two slab sums in one launch (the backward's column partials and its dR
-// slabs): workgroups [0, a.blocks) sum problem a, the rest problem b, each in
-// the layout and order of sum_slabs_kernel (plain: a thread per element, the
-// slabs in order) or sum_slabs_split_kernel (split: 64 columns per workgroup,
-// 16 slab groups, partials added in order), so results are the bits of the
-// separate launches.
-struct SlabSum {
-  const float* in;
-  int64_t nslab, n;
-  void* out;
-  int f64;     // out is double
-  int split;   // the split layout (few columns, many slabs)
-  int vec;     // 4 consecutive elements per thread (16-B loads): n % 4 == 0, aligned
-  int64_t blocks;
-};
-
-MPV_DEV void slab_store(const SlabSum& q, int64_t i, float v) {
-  if (q.f64)
-    reinterpret_cast<double*>(q.out)[i] = (double)v;
-  else
-    reinterpret_cast<float*>(q.out)[i] = v;
+// A thread per four consecutive elements (16-B loads); unrolled so that the
+// loads of several slabs are in flight together.
+MPV_DEV void slab_sum_vec(const SlabSum& q, int64_t blk) {
+  const int64_t i = (blk * 1024 + threadIdx.x) * 4;
+  if (i >= q.n) return;
+  f32x4 acc{0.f, 0.f, 0.f, 0.f};
+#pragma unroll 8
+  for (int64_t k = 0; k < q.nslab; ++k) acc += *reinterpret_cast<const f32x4*>(q.in + k * q.n + i);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) slab_store(q, i + j, acc[j]);
 }
 
-__global__ __launch_bounds__(1024) void sum_slabs_pair_kernel(SlabSum a, SlabSum b) {
+// A thread per element, THREADS per workgroup.
+template <int THREADS>
+MPV_DEV void slab_sum_plain(const SlabSum& q, int64_t blk) {
+  const int64_t i = blk * THREADS + threadIdx.x;
+  if (i >= q.n) return;
+  float acc = 0.0f;
+#pragma unroll 8
+  for (int64_t k = 0; k < q.nslab; ++k) acc += q.in[k * q.n + i];
+  slab_store(q, i, acc);
+}
+
+// Two slab sums in one launch (the backward's column partials and its dR
+// slabs): workgroups [0, a.blocks) sum problem a, the rest problem b.
+__global__ __launch_bounds__(1024) void sum_slabs_kernel(SlabSum a, SlabSum b) {
   __shared__ float part[16][65];
   const bool second = (int64_t)blockIdx.x >= a.blocks;
   const SlabSum q = second ? b : a;
   const int64_t blk = second ? (int64_t)blockIdx.x - a.blocks : (int64_t)blockIdx.x;
-  if (q.split) {
-    const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
-    const int64_t i = blk * 64 + lane;
-    float acc = 0.0f;
-    if (i < q.n) {
-#pragma unroll 4
-      for (int64_t k = g; k < q.nslab; k += 16) acc += q.in[k * q.n + i];
-    }
-    part[g][lane] = acc;
-    __syncthreads();
-    if (g == 0 && i < q.n) {
-      float t = part[0][lane];
-#pragma unroll
-      for (int j = 1; j < 16; ++j) t += part[j][lane];
-      slab_store(q, i, t);
-    }
-  } else if (q.vec) {  // the same sums, four elements per thread (16-B loads)
-    const int64_t i = (blk * 1024 + threadIdx.x) * 4;
-    if (i < q.n) {
-      f32x4 acc{0.f, 0.f, 0.f, 0.f};
-#pragma unroll 8
-      for (int64_t k = 0; k < q.nslab; ++k) acc += *reinterpret_cast<const f32x4*>(q.in + k * q.n + i);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) slab_store(q, i + j, acc[j]);
-    }
-  } else {
-    const int64_t i = blk * 1024 + threadIdx.x;
-    if (i < q.n) {
-      float acc = 0.0f;
-#pragma unroll 8
-      for (int64_t k = 0; k < q.nslab; ++k) acc += q.in[k * q.n + i];
-      slab_store(q, i, acc);
-    }
-  }
+  if (q.split)
+    slab_sum_split(q, blk, part);
+  else if (q.vec)
+    slab_sum_vec(q, blk);
+  else
+    slab_sum_plain<1024>(q, blk);
+}
+
+// One sum alone outside the split layout: the plain body in workgroups of
+// kSlabSingleThreads that stride over the q.blocks blocks of the problem (at
+// most 8192 workgroups), with no LDS behind them.  (In the pair kernel's
+// 1024-thread workgroups, which carry the split layout's LDS tile, the same sum
+// measured 1.6 % slower at C4's d fe_out | d fx_out, in either the vec or the
+// plain layout: profiles/operand_refactor_bench.json.)
+constexpr int kSlabSingleThreads = 256;
+__global__ __launch_bounds__(kSlabSingleThreads) void sum_slabs_plain_kernel(SlabSum q) {
+  for (int64_t blk = blockIdx.x; blk < q.blocks; blk += gridDim.x)
+    slab_sum_plain<kSlabSingleThreads>(q, blk);
 }
 
 // gathered (R,6,B) -> out (6,B)
@@ -306,32 +294,17 @@ __global__ void kl_bwd_kernel(mpv_kl_bwd_args a) {
 constexpr int kMaxBlocks = 1024;  // block maxima of maxabs_kernel (workspace size)
 constexpr int kSplitMaxBlocks = 256;  // maxabs blocks of mpv_split_f16 (read by every split wave)
 
-template <typename T>
-__global__ __launch_bounds__(256) void maxabs_kernel(const T* __restrict__ x, int64_t n,
-                                                    float* __restrict__ block_max) {
-  __shared__ float red[16];
-  float m = 0.0f;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x)
-    m = fmaxf(m, fabsf((float)x[i]));
-  m = block_reduce<true>(m, red);
-  if (threadIdx.x == 0) block_max[blockIdx.x] = m;
-}
-
-
-// maxabs_kernel on 16-B vectors with four independent maxima per thread (the
-// scalar loop kept a dependent max chain and few loads in flight: 10.6 us for
-// r_sqrt_sigma at C4).  x 16-B aligned; the n % VEC tail is block 0's.
-template <typename T>
-__global__ __launch_bounds__(256) void maxabs_vec_kernel(const T* __restrict__ x, int64_t n,
-                                                        float* __restrict__ block_max) {
-  constexpr int VEC = 16 / sizeof(T);
+// A thread's max |x| over the VEC-element vectors i, i + st, ... of x[0, n):
+// VEC 1, or 16 B / sizeof(T) for a 16-B aligned x (the n % VEC tail is the
+// caller's).  Four independent chains keep the loads in flight together (one
+// dependent chain over scalars took 10.6 us for r_sqrt_sigma at C4); a max is
+// exact in any order.
+template <int VEC, typename T, typename I>
+MPV_DEV float thread_maxabs(const T* __restrict__ x, I n, I i, I st) {
   typedef T vec_t __attribute__((ext_vector_type(VEC)));
-  __shared__ float red[16];
   const vec_t* xv = reinterpret_cast<const vec_t*>(x);
-  const int64_t nv = n / VEC, st = (int64_t)gridDim.x * blockDim.x;
+  const I nv = n / VEC;
   float m0 = 0.f, m1 = 0.f, m2 = 0.f, m3 = 0.f;
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   for (; i + 3 * st < nv; i += 4 * st) {
     const vec_t a = xv[i], b = xv[i + st], c = xv[i + 2 * st], d = xv[i + 3 * st];
 #pragma unroll
@@ -347,75 +320,86 @@ __global__ __launch_bounds__(256) void maxabs_vec_kernel(const T* __restrict__ x
 #pragma unroll
     for (int k = 0; k < VEC; ++k) m0 = fmaxf(m0, fabsf((float)a[k]));
   }
+  return fmaxf(fmaxf(m0, m1), fmaxf(m2, m3));
+}
+
+// block_max[block] = the block's max |x|; VEC as in thread_maxabs, the n % VEC
+// tail is block 0's.
+template <typename T, int VEC>
+__global__ __launch_bounds__(256) void maxabs_kernel(const T* __restrict__ x, int64_t n,
+                                                    float* __restrict__ block_max) {
+  __shared__ float red[16];
+  float m = thread_maxabs<VEC>(x, n, (int64_t)blockIdx.x * blockDim.x + threadIdx.x,
+                               (int64_t)gridDim.x * blockDim.x);
   if (blockIdx.x == 0)
-    for (int64_t j = nv * VEC + threadIdx.x; j < n; j += blockDim.x) m1 = fmaxf(m1, fabsf((float)x[j]));
-  float m = block_reduce<true>(fmaxf(fmaxf(m0, m1), fmaxf(m2, m3)), red);
+    for (int64_t j = n / VEC * VEC + threadIdx.x; j < n; j += blockDim.x)
+      m = fmaxf(m, fabsf((float)x[j]));
+  m = block_reduce<true>(m, red);
   if (threadIdx.x == 0) block_max[blockIdx.x] = m;
 }
 
-// split_kernel for cols % 8 == 0 and a 16-B aligned x: a thread splits 8
-// consecutive columns of one row (vector loads) and writes their hi and lo
-// halves as two 16-B stores (the scalar kernel's 2-B stores: 7.5 us for
-// r_sqrt_sigma at C4).  Same values as split_kernel.
-template <typename T>
-__global__ __launch_bounds__(256) void split8_kernel(const T* __restrict__ x, int64_t rows,
-                                                    int64_t cols, mpv_split16 out,
-                                                    const float* __restrict__ bmax, int nb) {
-  constexpr int VEC = 16 / sizeof(T);
+// The hi and the lo halves of 8 consecutive plane columns, a 16-B store each;
+// p points at the first hi half.
+MPV_DEV void store_hi_lo8(uint16_t* p, const uint16_t (&h)[8], const uint16_t (&l)[8]) {
+  *reinterpret_cast<s16x8*>(p) = s16x8{(short)h[0], (short)h[1], (short)h[2], (short)h[3],
+                                       (short)h[4], (short)h[5], (short)h[6], (short)h[7]};
+  *reinterpret_cast<s16x8*>(p + kLoOff) = s16x8{(short)l[0], (short)l[1], (short)l[2], (short)l[3],
+                                                (short)l[4], (short)l[5], (short)l[6], (short)l[7]};
+}
+
+// Columns c0 .. c0 + CPT - 1 of plane row r: x (rows, cols) row-major scaled by
+// s and split, zero outside the input.  CPT 1, or 8 for cols % 8 == 0, c0 % 8
+// == 0 and a 16-B aligned x: vector loads and two 16-B stores (the 2-B stores
+// took 7.5 us for r_sqrt_sigma at C4).
+template <int CPT, typename T, typename I>
+MPV_DEV void split_store(const T* __restrict__ x, I rows, I cols, const mpv_split16& out, float s,
+                         I r, I c0) {
+  static_assert(CPT == 1 || CPT == 8, "one column, or an 8-column group");
+  constexpr int VEC = CPT == 1 ? 1 : 16 / sizeof(T);
   typedef T vec_t __attribute__((ext_vector_type(VEC)));
-  const float s = wave_pow2_scale(bmax, nb);
-  if (blockIdx.x == 0 && threadIdx.x == 0) *out.scale = s;
-  const int64_t g8 = (out.ld >> 1) / 8;  // 8-column groups per plane row
-  const int64_t n = out.rows_pad * g8;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t r = i / g8, c0 = (i - r * g8) * 8;
-    float v[8];
-    if (r < rows && c0 < cols) {  // cols % 8 == 0: all 8 columns are in range
-      const vec_t* xv = reinterpret_cast<const vec_t*>(x + r * cols + c0);
+  float v[CPT];
+  if (r < rows && c0 < cols) {  // CPT 8: cols % 8 == 0, so all 8 columns are in range
+    const vec_t* xv = reinterpret_cast<const vec_t*>(x + r * cols + c0);
 #pragma unroll
-      for (int q = 0; q < 8 / VEC; ++q) {
-        const vec_t a = xv[q];
+    for (int q = 0; q < CPT / VEC; ++q) {
+      const vec_t a = xv[q];
 #pragma unroll
-        for (int k = 0; k < VEC; ++k) v[q * VEC + k] = (float)a[k];
-      }
-    } else {
-#pragma unroll
-      for (int k = 0; k < 8; ++k) v[k] = 0.0f;
+      for (int k = 0; k < VEC; ++k) v[q * VEC + k] = (float)a[k];
     }
-    uint16_t h[8], l[8];
+  } else {
 #pragma unroll
-    for (int k = 0; k < 8; ++k) split_f16(v[k], s, h[k], l[k]);
-    const int64_t o = chunked_index(r, out.ld, c0);
-    *reinterpret_cast<s16x8*>(out.data + o) =
-        s16x8{(short)h[0], (short)h[1], (short)h[2], (short)h[3], (short)h[4], (short)h[5], (short)h[6], (short)h[7]};
-    *reinterpret_cast<s16x8*>(out.data + o + kLoOff) =
-        s16x8{(short)l[0], (short)l[1], (short)l[2], (short)l[3], (short)l[4], (short)l[5], (short)l[6], (short)l[7]};
+    for (int k = 0; k < CPT; ++k) v[k] = 0.0f;
+  }
+  uint16_t h[CPT], l[CPT];
+#pragma unroll
+  for (int k = 0; k < CPT; ++k) split_f16(v[k], s, h[k], l[k]);
+  uint16_t* p = out.data + chunked_index(r, out.ld, c0);
+  if constexpr (CPT == 8) {
+    store_hi_lo8(p, h, l);
+  } else {
+    p[0] = h[0];
+    p[kLoOff] = l[0];
   }
 }
 
 // (rows, cols) row-major -> chunked split planes (rows_pad x ld/2 columns),
-// zero padded.  Thread i owns logical element (r, c) = (i / cols_pad, i % cols_pad).
-// The scale comes from the nb block maxima of maxabs_kernel, taken by every
-// wave itself (wave_pow2_scale: the same bits as a scale launch of its own,
-// one launch fewer); block 0 publishes it.
-template <typename T>
+// zero padded.  Thread i owns the CPT columns (split_store) from c0 = (i % g)
+// CPT of plane row i / g, g = ld / 2 / CPT.  The scale comes from the nb block
+// maxima of maxabs_kernel, taken by every wave itself (wave_pow2_scale: the
+// same bits as a scale launch of its own, one launch fewer); block 0
+// publishes it.
+template <typename T, int CPT>
 __global__ __launch_bounds__(256) void split_kernel(const T* __restrict__ x, int64_t rows,
                                                    int64_t cols, mpv_split16 out,
                                                    const float* __restrict__ bmax, int nb) {
   const float s = wave_pow2_scale(bmax, nb);
   if (blockIdx.x == 0 && threadIdx.x == 0) *out.scale = s;
-  const int64_t cp = out.ld >> 1;
-  const int64_t n = out.rows_pad * cp;
+  const int64_t g = (out.ld >> 1) / CPT;
+  const int64_t n = out.rows_pad * g;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t r = i / cp, c = i - r * cp;
-    const float v = (r < rows && c < cols) ? (float)x[r * cols + c] : 0.0f;
-    uint16_t h, l;
-    split_f16(v, s, h, l);
-    const int64_t o = chunked_index(r, out.ld, c);
-    out.data[o] = h;
-    out.data[o + kLoOff] = l;
+    const int64_t r = i / g;
+    split_store<CPT>(x, rows, cols, out, s, r, (i - r * g) * CPT);
   }
 }
 
@@ -431,30 +415,13 @@ template <typename T>
 MPV_DEV void split_small_body(const T* __restrict__ x, int rows, int cols, const mpv_split16& out,
                               int blk, int nblk) {
   __shared__ float red[16];
-  const int n = rows * cols, st = blockDim.x;
-  // four independent chains (the loads in flight together; a max is exact in
-  // any order)
-  float m0 = 0.0f, m1 = 0.0f, m2 = 0.0f, m3 = 0.0f;
-  int i = threadIdx.x;
-  for (; i + 3 * st < n; i += 4 * st) {
-    m0 = fmaxf(m0, fabsf((float)x[i]));
-    m1 = fmaxf(m1, fabsf((float)x[i + st]));
-    m2 = fmaxf(m2, fabsf((float)x[i + 2 * st]));
-    m3 = fmaxf(m3, fabsf((float)x[i + 3 * st]));
-  }
-  for (; i < n; i += st) m0 = fmaxf(m0, fabsf((float)x[i]));
-  const float m = fmaxf(fmaxf(m0, m1), fmaxf(m2, m3));
+  const float m = thread_maxabs<1>(x, rows * cols, (int)threadIdx.x, (int)blockDim.x);
   const float s = pow2_scale(block_reduce<true>(m, red));
   if (blk == 0 && threadIdx.x == 0) *out.scale = s;
   const int cp = (int)(out.ld >> 1), np = (int)out.rows_pad * cp;
   for (int i = blk * blockDim.x + threadIdx.x; i < np; i += nblk * blockDim.x) {
-    const int r = i / cp, c = i - r * cp;
-    const float v = (r < rows && c < cols) ? (float)x[r * cols + c] : 0.0f;
-    uint16_t h, l;
-    split_f16(v, s, h, l);
-    const int64_t o = chunked_index(r, out.ld, c);
-    out.data[o] = h;
-    out.data[o + kLoOff] = l;
+    const int r = i / cp;
+    split_store<1>(x, rows, cols, out, s, r, i - r * cp);
   }
 }
 
@@ -467,7 +434,7 @@ __global__ __launch_bounds__(256) void split_small_kernel(const T* __restrict__ 
 // A small operand split riding on the noise launch (mpv_noise_philox_f16_split).
 struct SmallSplit {
   const void* x;
-  int f64, rows, cols;
+  int dtype, rows, cols;  // MPV_F32 / MPV_F64
   mpv_split16 out;
   int nblocks;  // the grid's last nblocks workgroups split; 0: none
 };
@@ -552,9 +519,8 @@ __host__ __device__ inline int noise_narrow_tpr(int z) { return (z + kNoiseCols 
 template <int CPT>
 MPV_DEV void noise16_zero_tail(const mpv_split16& out, int r, int c_first, int cols) {
   for (int c0 = c_first; c0 < cols; c0 += CPT) {
-    const int64_t o = chunked_index(r, out.ld, c0);
-    *reinterpret_cast<s16x8*>(out.data + o) = s16x8{0, 0, 0, 0, 0, 0, 0, 0};
-    *reinterpret_cast<s16x8*>(out.data + o + kLoOff) = s16x8{0, 0, 0, 0, 0, 0, 0, 0};
+    const uint16_t zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    store_hi_lo8(out.data + chunked_index(r, out.ld, c0), zero, zero);
   }
 }
 
@@ -573,15 +539,8 @@ MPV_DEV void noise16_row(const mpv_split16& out, int S, int B, int z, int64_t s_
     uint16_t h[CPT], l[CPT];
 #pragma unroll
     for (int q = 0; q < CPT; ++q) split_f16(v[q], kNoiseScale, h[q], l[q]);
-    static_assert(CPT == 8, "two 16-B stores per thread");
-    const int64_t o = chunked_index(r, out.ld, c0);
-    const s16x8 hv{(short)h[0], (short)h[1], (short)h[2], (short)h[3],
-                   (short)h[4], (short)h[5], (short)h[6], (short)h[7]};
-    const s16x8 lv{(short)l[0], (short)l[1], (short)l[2], (short)l[3],
-                   (short)l[4], (short)l[5], (short)l[6], (short)l[7]};
     // plain stores (nontemporal ones measured slower: DESIGN.md section 3)
-    *reinterpret_cast<s16x8*>(out.data + o) = hv;
-    *reinterpret_cast<s16x8*>(out.data + o + kLoOff) = lv;
+    store_hi_lo8(out.data + chunked_index(r, out.ld, c0), h, l);
   }
 }
 
@@ -594,12 +553,10 @@ __global__ __launch_bounds__(256) void noise_philox16_kernel(mpv_split16 out, in
   // r_sqrt_sigma's split, beside the noise (one launch): the first workgroups,
   // so that they start with the noise's and finish under it
   if ((int)blockIdx.x < ss.nblocks) {
-    if (ss.f64)
-      split_small_body<double>((const double*)ss.x, ss.rows, ss.cols, ss.out, blockIdx.x,
-                               ss.nblocks);
-    else
-      split_small_body<float>((const float*)ss.x, ss.rows, ss.cols, ss.out, blockIdx.x,
-                              ss.nblocks);
+    with_dtype(ss.dtype, [&](auto t) {
+      typedef decltype(t) T;
+      split_small_body((const T*)ss.x, ss.rows, ss.cols, ss.out, (int)blockIdx.x, ss.nblocks);
+    });
     return;
   }
   const int nblk = (int)blockIdx.x - ss.nblocks;  // this workgroup's noise block
@@ -730,46 +687,30 @@ int mpv_split_f16(const void* x, int x_dtype, int64_t rows, int64_t cols, const 
   MPV_REQUIRE(x_dtype == MPV_F32 || x_dtype == MPV_F64, "unsupported dtype %d", x_dtype);
   hipStream_t s = as_stream(stream);
   const int64_t plane_elems = out->rows_pad * (out->ld / 2);
-  if (rows * cols <= kSplitSmall && plane_elems < (int64_t(1) << 31)) {
-    const dim3 g((unsigned)std::min<int64_t>(cdiv(plane_elems, 256 * 4), 256));
-    if (x_dtype == MPV_F64)
-      MPV_LAUNCH("split", split_small_kernel<double>, g, dim3(256), 0, s, (const double*)x,
-                 (int)rows, (int)cols, *out);
-    else
-      MPV_LAUNCH("split", split_small_kernel<float>, g, dim3(256), 0, s, (const float*)x,
-                 (int)rows, (int)cols, *out);
-    return check_launch("split_f16");
-  }
-  float* bmax = reinterpret_cast<float*>(workspace);
   const int64_t n = rows * cols;
-  const unsigned g = grid_for(n, 256, kSplitMaxBlocks);
   const bool aligned = (reinterpret_cast<uintptr_t>(x) & 15) == 0;
-  const bool f64 = x_dtype == MPV_F64;
-  if (aligned && f64)
-    MPV_LAUNCH("split", maxabs_vec_kernel<double>, dim3(g), dim3(256), 0, s, (const double*)x, n, bmax);
-  else if (aligned)
-    MPV_LAUNCH("split", maxabs_vec_kernel<float>, dim3(g), dim3(256), 0, s, (const float*)x, n, bmax);
-  else if (f64)
-    MPV_LAUNCH("split", maxabs_kernel<double>, dim3(g), dim3(256), 0, s, (const double*)x, n, bmax);
-  else
-    MPV_LAUNCH("split", maxabs_kernel<float>, dim3(g), dim3(256), 0, s, (const float*)x, n, bmax);
-  if (aligned && cols % 8 == 0) {  // whole 8-column groups: vector loads, 16-B stores
-    const unsigned g2 = grid_for(out->rows_pad * (out->ld / 2) / 8, 256, 16384);
-    if (f64)
-      MPV_LAUNCH("split", split8_kernel<double>, dim3(g2), dim3(256), 0, s, (const double*)x, rows,
-                 cols, *out, bmax, (int)g);
+  with_dtype(x_dtype, [&](auto t) {
+    typedef decltype(t) T;
+    const T* xt = reinterpret_cast<const T*>(x);
+    const dim3 b(256);
+    if (n <= kSplitSmall && plane_elems < (int64_t(1) << 31)) {
+      const dim3 g((unsigned)std::min<int64_t>(cdiv(plane_elems, 256 * 4), 256));
+      MPV_LAUNCH("split", split_small_kernel<T>, g, b, 0, s, xt, (int)rows, (int)cols, *out);
+      return;
+    }
+    float* bmax = reinterpret_cast<float*>(workspace);
+    const unsigned g = grid_for(n, 256, kSplitMaxBlocks);
+    if (aligned)
+      MPV_LAUNCH("split", (maxabs_kernel<T, 16 / sizeof(T)>), dim3(g), b, 0, s, xt, n, bmax);
     else
-      MPV_LAUNCH("split", split8_kernel<float>, dim3(g2), dim3(256), 0, s, (const float*)x, rows,
-                 cols, *out, bmax, (int)g);
-    return check_launch("split_f16");
-  }
-  const unsigned g2 = grid_for(out->rows_pad * (out->ld / 2), 256, 16384);
-  if (f64)
-    MPV_LAUNCH("split", split_kernel<double>, dim3(g2), dim3(256), 0, s, (const double*)x, rows,
-               cols, *out, bmax, (int)g);
-  else
-    MPV_LAUNCH("split", split_kernel<float>, dim3(g2), dim3(256), 0, s, (const float*)x, rows,
-               cols, *out, bmax, (int)g);
+      MPV_LAUNCH("split", (maxabs_kernel<T, 1>), dim3(g), b, 0, s, xt, n, bmax);
+    if (aligned && cols % 8 == 0)  // whole 8-column groups: vector loads, 16-B stores
+      MPV_LAUNCH("split", (split_kernel<T, 8>), dim3(grid_for(plane_elems / 8, 256, 16384)), b, 0,
+                 s, xt, rows, cols, *out, bmax, (int)g);
+    else
+      MPV_LAUNCH("split", (split_kernel<T, 1>), dim3(grid_for(plane_elems, 256, 16384)), b, 0, s,
+                 xt, rows, cols, *out, bmax, (int)g);
+  });
   return check_launch("split_f16");
 }
 
@@ -824,7 +765,7 @@ int mpv_noise_philox_f16_split(const mpv_shape* shape, uint64_t seed, const uint
   MPV_REQUIRE(rows <= x_out->rows_pad && cols <= x_out->ld / 2, "planes smaller than the input");
   MPV_REQUIRE(x_out->rows_pad * (x_out->ld / 2) < (int64_t(1) << 31), "planes too large");
   MPV_REQUIRE(x_dtype == MPV_F32 || x_dtype == MPV_F64, "unsupported dtype %d", x_dtype);
-  SmallSplit ss{x, x_dtype == MPV_F64, (int)rows, (int)cols, *x_out, 0};
+  SmallSplit ss{x, x_dtype, (int)rows, (int)cols, *x_out, 0};
   return noise_philox_f16(shape, seed, seed_dev, offset, out, stream, ss);
 }
 
@@ -835,18 +776,14 @@ int mpv_convert(const void* src, int sd, void* dst, int dd, int64_t n, void* str
   if (n == 0) return MPV_OK;
   const unsigned g = grid_for(n, 256);
   hipStream_t s = as_stream(stream);
-  if (sd == MPV_F64 && dd == MPV_F32)
-    MPV_LAUNCH("convert", (convert_kernel<double, float>), dim3(g), dim3(256), 0, s,
-                       (const double*)src, (float*)dst, n);
-  else if (sd == MPV_F32 && dd == MPV_F64)
-    MPV_LAUNCH("convert", (convert_kernel<float, double>), dim3(g), dim3(256), 0, s,
-                       (const float*)src, (double*)dst, n);
-  else if (sd == MPV_F32)
-    MPV_LAUNCH("convert", (convert_kernel<float, float>), dim3(g), dim3(256), 0, s,
-                       (const float*)src, (float*)dst, n);
-  else
-    MPV_LAUNCH("convert", (convert_kernel<double, double>), dim3(g), dim3(256), 0, s,
-                       (const double*)src, (double*)dst, n);
+  with_dtype(sd, [&](auto from) {
+    with_dtype(dd, [&](auto to) {
+      typedef decltype(from) S;
+      typedef decltype(to) D;
+      MPV_LAUNCH("convert", (convert_kernel<S, D>), dim3(g), dim3(256), 0, s,
+                 reinterpret_cast<const S*>(src), reinterpret_cast<D*>(dst), n);
+    });
+  });
   return check_launch("convert");
 }
 
@@ -895,51 +832,49 @@ int mpv_kl_bwd(const mpv_kl_bwd_args* a, void* stream) {
 }  // extern "C"
 
 namespace mpv {
-// Used by the forward / backward translation units.
+// The slab sums' host side (abi_util.h: the forward and backward translation
+// units call them).
 
+// The layout rule, in this one place (slab_sum_is_split, abi_util.h, is its
+// split half: predict_final mirrors it).  n == 0: the empty problem, no
+// workgroup.
 static SlabSum slab_problem(const float* in, int64_t nslab, int64_t n, void* out, int out_dtype) {
   SlabSum q;
   q.in = in;
   q.nslab = nslab;
   q.n = n;
   q.out = out;
-  q.f64 = out_dtype == MPV_F64;
-  q.split = nslab >= 64 && n <= 256 * 256;  // the rule of launch_sum_slabs
+  q.out_dtype = out_dtype;
+  q.split = slab_sum_is_split(nslab, n);
   q.vec = !q.split && n % 4 == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0;
   q.blocks = q.split ? cdiv(n, 64) : (q.vec ? cdiv(n, 4096) : cdiv(n, 1024));
   return q;
 }
 
-int launch_sum_slabs_pair(const float* in0, int64_t nslab0, int64_t n0, void* out0,
-                          int out0_dtype, const float* in1, int64_t nslab1, int64_t n1,
-                          void* out1, int out1_dtype, hipStream_t s) {
-  const SlabSum a = slab_problem(in0, nslab0, n0, out0, out0_dtype);
-  const SlabSum b = slab_problem(in1, nslab1, n1, out1, out1_dtype);
+static int launch_slab_pair(const SlabSum& a, const SlabSum& b, hipStream_t s) {
+  if (a.blocks + b.blocks == 0) return MPV_OK;
   MPV_REQUIRE(a.blocks + b.blocks < (int64_t(1) << 31), "slab sums too large");
-  MPV_LAUNCH("sum_slabs", sum_slabs_pair_kernel, dim3((unsigned)(a.blocks + b.blocks)), dim3(1024),
-             0, s, a, b);
+  MPV_LAUNCH("sum_slabs", sum_slabs_kernel, dim3((unsigned)(a.blocks + b.blocks)), dim3(1024), 0,
+             s, a, b);
   return check_launch("sum_slabs");
 }
 
+int launch_sum_slabs_pair(const float* in0, int64_t nslab0, int64_t n0, void* out0,
+                          int out0_dtype, const float* in1, int64_t nslab1, int64_t n1,
+                          void* out1, int out1_dtype, hipStream_t s) {
+  return launch_slab_pair(slab_problem(in0, nslab0, n0, out0, out0_dtype),
+                          slab_problem(in1, nslab1, n1, out1, out1_dtype), s);
+}
+
+// One sum alone: the split layout is the pair with an empty second problem;
+// any other goes to sum_slabs_plain_kernel.
 int launch_sum_slabs(const float* in, int64_t nslab, int64_t n, void* out, int out_dtype,
                      hipStream_t s) {
-  if (nslab >= 64 && n <= 256 * 256) {  // too few columns to hide the slab chain
-    const unsigned gs = (unsigned)((n + 63) / 64);
-    if (out_dtype == MPV_F64)
-      MPV_LAUNCH("sum_slabs", (sum_slabs_split_kernel<double>), dim3(gs), dim3(1024), 0, s, in,
-                 nslab, n, (double*)out);
-    else
-      MPV_LAUNCH("sum_slabs", (sum_slabs_split_kernel<float>), dim3(gs), dim3(1024), 0, s, in,
-                 nslab, n, (float*)out);
-    return check_launch("sum_slabs");
-  }
-  const unsigned g = grid_for(n, 256, 8192);
-  if (out_dtype == MPV_F64)
-    MPV_LAUNCH("sum_slabs", (sum_slabs_kernel<double>), dim3(g), dim3(256), 0, s, in, nslab, n,
-                       (double*)out);
-  else
-    MPV_LAUNCH("sum_slabs", (sum_slabs_kernel<float>), dim3(g), dim3(256), 0, s, in, nslab, n,
-                       (float*)out);
+  SlabSum q = slab_problem(in, nslab, n, out, out_dtype);
+  if (q.split || n == 0) return launch_slab_pair(q, slab_problem(nullptr, 0, 0, nullptr, MPV_F32), s);
+  q.blocks = cdiv(n, kSlabSingleThreads);
+  MPV_LAUNCH("sum_slabs", sum_slabs_plain_kernel, dim3((unsigned)std::min<int64_t>(q.blocks, 8192)),
+             dim3(kSlabSingleThreads), 0, s, q);
   return check_launch("sum_slabs");
 }
 }  // namespace mpv

@@ -56,6 +56,7 @@ class Planes:
 
 
 GEMMS = {"f16x3": H.GEMM_F16X3, "f32": H.GEMM_F32}
+DTYPE_TAGS = {torch.float32: H.F32, torch.float64: H.F64}
 
 
 def eps_cols(shape):
@@ -146,16 +147,15 @@ class HipShardBackend:
         Rop = Planes(_pad(L, 256), _pad(z, 128), R.device)
         H.check(lib.mpv_noise_philox_f16_split(
             shape, 0 if dev_key else int(seed) & (2 ** 64 - 1), H.ptr(seed) if dev_key else None,
-            offset, eps.c(), H.ptr(Rc), H.F64 if Rc.dtype == torch.float64 else H.F32, L, z,
-            Rop.c(), st), "mpv_noise_philox_f16_split")
+            offset, eps.c(), H.ptr(Rc), DTYPE_TAGS[Rc.dtype], L, z, Rop.c(), st),
+            "mpv_noise_philox_f16_split")
         return eps, Rop
 
     def _split(self, x, rows, cols, planes):
         lib = H.load_library()
         ws = torch.empty((lib.mpv_split_workspace_bytes(),), device=x.device, dtype=torch.uint8)
-        dt = H.F64 if x.dtype == torch.float64 else H.F32
-        H.check(lib.mpv_split_f16(H.ptr(x), dt, rows, cols, planes.c(), H.ptr(ws),
-                                  H.stream_of(x.device)), "mpv_split_f16")
+        H.check(lib.mpv_split_f16(H.ptr(x), DTYPE_TAGS[x.dtype], rows, cols, planes.c(),
+                                  H.ptr(ws), H.stream_of(x.device)), "mpv_split_f16")
         return planes
 
     def prepare_noise(self, eps, shape):
@@ -182,19 +182,33 @@ class HipShardBackend:
             return R.contiguous()
         if R.dtype != torch.float64:
             raise TypeError(f"r_sqrt_sigma must be float32 or float64 (got {R.dtype})")
-        R = R.contiguous()
-        out = torch.empty(R.shape, device=R.device, dtype=torch.float32)
-        H.check(H.load_library().mpv_convert(H.ptr(R), H.F64, H.ptr(out), H.F32, R.numel(),
-                                             H.stream_of(R.device)), "mpv_convert")
-        return out
+        return self._convert(R.contiguous(), torch.float32)
 
     def from_f32(self, x32, dtype):
-        if dtype == torch.float32:
-            return x32
-        out = torch.empty(x32.shape, device=x32.device, dtype=dtype)
-        H.check(H.load_library().mpv_convert(H.ptr(x32), H.F32, H.ptr(out), H.F64, x32.numel(),
-                                             H.stream_of(x32.device)), "mpv_convert")
+        return x32 if dtype == torch.float32 else self._convert(x32, dtype)
+
+    @staticmethod
+    def _convert(x, dtype):
+        """Contiguous fp32 / fp64 x as a new tensor of dtype (mpv_convert)."""
+        out = torch.empty(x.shape, device=x.device, dtype=dtype)
+        H.check(H.load_library().mpv_convert(H.ptr(x), DTYPE_TAGS[x.dtype], H.ptr(out),
+                                             DTYPE_TAGS[dtype], x.numel(),
+                                             H.stream_of(x.device)), "mpv_convert")
         return out
+
+    def _eps_operands(self, eps):
+        """The (eps, eps16) slots of the kernels' argument structs: the 3xf16
+        noise planes or the fp32 pointer, the other mode's slot empty."""
+        if self.gemm == H.GEMM_F16X3:
+            return None, eps.c()
+        return H.ptr(eps), H.Split16()
+
+    def _gemm_operands(self, Rop, eps):
+        """The (R32, eps, R16, eps16) slots: r_sqrt_sigma beside _eps_operands."""
+        eps32, eps16 = self._eps_operands(eps)
+        if self.gemm == H.GEMM_F16X3:
+            return None, eps32, Rop.c(), eps16
+        return H.ptr(Rop), eps32, H.Split16(), eps16
 
     def forward_local(self, shape, y, fe_out, fx_out, Rop, eps, keep_T, stat_slots=None):
         """stat_slots = (world, slot): colsum and bstat are written into one
@@ -222,11 +236,8 @@ class HipShardBackend:
             bstat = packed[n + slot * 6 * B:n + (slot + 1) * 6 * B].view(6, B)
         nbytes = lib.mpv_fwd_workspace_bytes(shape)
         ws = self._buf((max(nbytes, 1),), dev, torch.uint8)
-        if self.gemm == H.GEMM_F16X3:
-            ops = (None, None, Rop.c(), eps.c())
-        else:
-            ops = (H.ptr(Rop), H.ptr(eps), H.Split16(), H.Split16())
-        args = H.FwdArgs(H.ptr(y), H.ptr(fe_out), H.ptr(fx_out), self.gemm, *ops, H.ptr(T),
+        args = H.FwdArgs(H.ptr(y), H.ptr(fe_out), H.ptr(fx_out), self.gemm,
+                         *self._gemm_operands(Rop, eps), H.ptr(T),
                          H.ptr(rowstat), H.ptr(bstat), H.ptr(colsum), H.ptr(ws), nbytes)
         H.check(lib.mpv_probit_fwd(shape, args, H.stream_of(dev)), "mpv_probit_fwd")
         return dict(rowstat=rowstat, bstat=bstat, colsum=colsum, T=T, packed=packed)
@@ -244,11 +255,8 @@ class HipShardBackend:
         indiv = self._buf((B, L), dev, torch.float32) if want_indiv else None
         nbytes = lib.mpv_predict_workspace_bytes(shape)
         ws = self._buf((max(nbytes, 1),), dev, torch.uint8)
-        if self.gemm == H.GEMM_F16X3:
-            ops = (None, None, Rop.c(), eps.c())
-        else:
-            ops = (H.ptr(Rop), H.ptr(eps), H.Split16(), H.Split16())
-        args = H.PredictArgs(H.ptr(fx_out), self.gemm, *ops, H.ptr(colsum), H.ptr(indiv),
+        args = H.PredictArgs(H.ptr(fx_out), self.gemm, *self._gemm_operands(Rop, eps),
+                             H.ptr(colsum), H.ptr(indiv),
                              H.ptr(seed_advance), H.ptr(ws), nbytes)
         H.check(lib.mpv_probit_predict(shape, args, H.stream_of(dev)), "mpv_probit_predict")
         return colsum, indiv
@@ -325,15 +333,14 @@ class HipShardBackend:
         dR = flat[n_fe:].view(L, z) if with_32 else dR64
         nbytes = lib.mpv_bwd_workspace_bytes(shape, self.gemm)
         ws = self._buf((max(nbytes, 1),), dev, torch.uint8)
-        eps = saved["eps"]
-        eps_ops = (None, eps.c()) if self.gemm == H.GEMM_F16X3 else (H.ptr(eps), H.Split16())
         kl_outs, kl_ref = None, None
         if kl:
             kl_args, kl_outs = self._kl_args(saved["fe_mu"], saved["fe_logvar"], saved["fx_mu"],
                                              saved["fx_logvar"], gscal, live)
             kl_ref = ctypes.byref(kl_args)
         args = H.BwdArgs(H.ptr(saved["y"]), H.ptr(saved["fe_out"]), H.ptr(saved["fx_out"]),
-                         self.gemm, *eps_ops, H.ptr(saved["T"]), H.ptr(saved["rowstat"]),
+                         self.gemm, *self._eps_operands(saved["eps"]), H.ptr(saved["T"]),
+                         H.ptr(saved["rowstat"]),
                          H.ptr(saved["bstat"]), H.ptr(gscal), H.ptr(g_I), H.ptr(g_IL),
                          nll_coeff, c_coeff, live, H.ptr(dfe_dfx),
                          H.ptr(dR if with_32 else None), H.ptr(ws), nbytes, H.ptr(dR64),
@@ -391,6 +398,23 @@ class ElboConfig:
         self.exchange = exchange if exchange is not None else LocalExchange()
 
 
+def _operands(be, cfg, shape, device, R, eps):
+    """(eps, Rop): the noise and r_sqrt_sigma as the backend's GEMM operands.
+    Philox noise (cfg.noise) is drawn on the device -- a small r_sqrt_sigma's
+    split rides on that launch (make_noise_and_R) -- explicit noise is eps."""
+    if cfg.noise == "philox" and hasattr(be, "make_noise_and_R"):
+        return be.make_noise_and_R(shape, device, cfg.seed, cfg.offset, R)
+    if cfg.noise == "philox":
+        eps = be.make_noise(shape, device, cfg.seed, cfg.offset)
+    else:
+        eps = _f32(eps, "noise")
+        want = (cfg.S_local, shape.B, shape.z)
+        if tuple(eps.shape) != want:
+            raise ValueError(f"noise must be {want}, got {tuple(eps.shape)}")
+        eps = be.prepare_noise(eps, shape)
+    return eps, be.prepare_R(R)
+
+
 def probit_predict(fx_out, R, eps, cfg):
     """indiv_prob = mean_s E_x (mpvae.py:180, 203) alone, with no labels, no
     label branch and no loss terms: ProbitELBO.forward's noise and operand
@@ -408,18 +432,7 @@ def probit_predict(fx_out, R, eps, cfg):
         z = R.shape[1]
         cfg.exchange.verify_replicas((fx_out, R), names=("fx_out", "r_sqrt_sigma"))
         shape = be.shape(cfg.S_local, cfg.S_total, cfg.s_offset, B, L, z)
-        if cfg.noise == "philox" and hasattr(be, "make_noise_and_R"):
-            eps, Rop = be.make_noise_and_R(shape, fx_out.device, cfg.seed, cfg.offset, R)
-        else:
-            if cfg.noise == "philox":
-                eps = be.make_noise(shape, fx_out.device, cfg.seed, cfg.offset)
-            else:
-                eps = _f32(eps, "noise")
-                if tuple(eps.shape) != (cfg.S_local, B, z):
-                    raise ValueError(f"noise must be {(cfg.S_local, B, z)}, "
-                                     f"got {tuple(eps.shape)}")
-                eps = be.prepare_noise(eps, shape)
-            Rop = be.prepare_R(R)
+        eps, Rop = _operands(be, cfg, shape, fx_out.device, R, eps)
         sharded = hasattr(cfg.exchange, "reduce_colsum")  # SampleShardExchange, not LocalExchange
         colsum, indiv = be.predict_local(shape, fx_out, Rop, eps, want_indiv=not sharded,
                                          seed_advance=cfg.seed_advance)
@@ -446,19 +459,7 @@ class ProbitELBO(torch.autograd.Function):
         z = R.shape[1]
         cfg.exchange.verify_replicas((y, fe_out, fx_out, R))
         shape = be.shape(cfg.S_local, cfg.S_total, cfg.s_offset, B, L, z)
-        if cfg.noise == "philox" and hasattr(be, "make_noise_and_R"):
-            # small r_sqrt_sigma: its split rides on the noise launch
-            eps, Rop = be.make_noise_and_R(shape, y.device, cfg.seed, cfg.offset, R)
-        else:
-            if cfg.noise == "philox":
-                eps = be.make_noise(shape, y.device, cfg.seed, cfg.offset)
-            else:
-                eps = _f32(eps, "noise")
-                if tuple(eps.shape) != (cfg.S_local, B, z):
-                    raise ValueError(f"noise must be {(cfg.S_local, B, z)}, "
-                                     f"got {tuple(eps.shape)}")
-                eps = be.prepare_noise(eps, shape)
-            Rop = be.prepare_R(R)
+        eps, Rop = _operands(be, cfg, shape, y.device, R, eps)
         need = ctx.needs_input_grad
         keep_T = need[1] or need[4] or need[7]
         fin = (fe_mu, fe_logvar, fx_mu, fx_logvar, cfg.nll_coeff, cfg.c_coeff)
