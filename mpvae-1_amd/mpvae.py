@@ -330,27 +330,42 @@ def _backend_for(tensors):
     return None
 
 
-def compute_loss(input_label, fe_out, fe_mu, fe_logvar, fx_out, fx_mu, fx_logvar,
-                 r_sqrt_sigma, args):
-    """Multivariate-probit ELBO of reference mpvae.py:145-210 (8-tuple)."""
-    host_be = _backend_for((input_label, fe_out, fe_mu, fe_logvar, fx_out, fx_mu, fx_logvar,
-                            r_sqrt_sigma))
+def _elbo_setup(tensors, out, r_sqrt_sigma, args):
+    """What compute_loss and predict_proba read of ``args``, in two halves.
+    Here: the backend for the tensors' device, the sample count of args.mode,
+    the batch (the rows of ``out``) and the checks of r_sqrt_sigma and the
+    sample count.  In the returned ``build(nll_coeff, c_coeff) -> (noise tensor
+    or None, ElboConfig)``, which the caller calls once its own checks and the
+    empty batch are behind it: this rank's shard, the noise source (a
+    torch_cpu draw happens there) and the gemm / backend / exchange wiring."""
+    host_be = _backend_for(tensors)
     n_sample = args.n_train_sample if args.mode == "train" else args.n_test_sample
-    B, z = fe_out.shape[0], args.z_dim
+    B, z = out.shape[0], args.z_dim
     if r_sqrt_sigma.dim() != 2 or r_sqrt_sigma.shape[1] != z:
         raise ValueError(f"r_sqrt_sigma must be (label_dim, z_dim={z}), "
                          f"got {tuple(r_sqrt_sigma.shape)}")
     if n_sample <= 0:
         # the reference's max over an empty sample axis (mpvae.py:188)
         raise IndexError(f"n_sample = {n_sample}: the Monte-Carlo sample axis is empty")
-    if B == 0:
+
+    def build(nll_coeff, c_coeff):
+        shard = mpvae_dist.shard_for(args, n_sample)
+        noise, kw = _noise_source(args, n_sample, B, z, shard, out.device)
+        return noise, ElboConfig(n_sample, shard.S_local, shard.s_offset, nll_coeff, c_coeff,
+                                 exchange=shard.exchange, backend=host_be,
+                                 gemm=getattr(args, "mpvae_gemm", "f16x3"), **kw)
+    return build
+
+
+def compute_loss(input_label, fe_out, fe_mu, fe_logvar, fx_out, fx_mu, fx_logvar,
+                 r_sqrt_sigma, args):
+    """Multivariate-probit ELBO of reference mpvae.py:145-210 (8-tuple)."""
+    build = _elbo_setup((input_label, fe_out, fe_mu, fe_logvar, fx_out, fx_mu, fx_logvar,
+                         r_sqrt_sigma), fe_out, r_sqrt_sigma, args)
+    if fe_out.shape[0] == 0:
         return _empty_batch(fe_out, fe_mu, fe_logvar, fx_out, fx_mu, fx_logvar, r_sqrt_sigma,
                             args)
-    shard = mpvae_dist.shard_for(args, n_sample)
-    noise, kw = _noise_source(args, n_sample, B, z, shard, fe_out.device)
-    cfg = ElboConfig(n_sample, shard.S_local, shard.s_offset, args.nll_coeff, args.c_coeff,
-                     exchange=shard.exchange, gemm=getattr(args, "mpvae_gemm", "f16x3"),
-                     backend=host_be, **kw)
+    noise, cfg = build(args.nll_coeff, args.c_coeff)
     return ProbitELBO.apply(input_label.float(), fe_out, fe_mu, fe_logvar, fx_out, fx_mu,
                             fx_logvar, r_sqrt_sigma, noise, cfg)
 
@@ -375,21 +390,10 @@ def predict_proba(fx_out, r_sqrt_sigma, args):
 
     No autograd: the result has no grad_fn whatever the grad mode and whether
     or not the inputs require gradients."""
-    host_be = _backend_for((fx_out, r_sqrt_sigma))
-    n_sample = args.n_train_sample if args.mode == "train" else args.n_test_sample
-    B, z = fx_out.shape[0], args.z_dim
-    if r_sqrt_sigma.dim() != 2 or r_sqrt_sigma.shape[1] != z:
-        raise ValueError(f"r_sqrt_sigma must be (label_dim, z_dim={z}), "
-                         f"got {tuple(r_sqrt_sigma.shape)}")
-    if n_sample <= 0:
-        raise IndexError(f"n_sample = {n_sample}: the Monte-Carlo sample axis is empty")
+    build = _elbo_setup((fx_out, r_sqrt_sigma), fx_out, r_sqrt_sigma, args)
     if fx_out.dim() != 2:
         raise ValueError(f"fx_out must be (batch, label_dim), got {tuple(fx_out.shape)}")
-    if B == 0:
+    if fx_out.shape[0] == 0:
         return torch.empty((0, fx_out.shape[1]), dtype=torch.float32, device=fx_out.device)
-    shard = mpvae_dist.shard_for(args, n_sample)
-    noise, kw = _noise_source(args, n_sample, B, z, shard, fx_out.device)
-    cfg = ElboConfig(n_sample, shard.S_local, shard.s_offset, 0.0, 0.0,
-                     exchange=shard.exchange, gemm=getattr(args, "mpvae_gemm", "f16x3"),
-                     backend=host_be, **kw)
+    noise, cfg = build(0.0, 0.0)
     return probit_predict(fx_out, r_sqrt_sigma, noise, cfg)

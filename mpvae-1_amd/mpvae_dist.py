@@ -11,7 +11,7 @@ order) is:
             log-sum-exp statistics bstat (6 x B floats: local max m and sum Z
             of exp(logp - m) per branch + ranking sums)], each rank's bstat in
             its own slot and zeros elsewhere, so the sum is also the exact
-            all_gather of bstat; combined as M = max m_r, Z = sum Z_r
+            gather of bstat; combined as M = max m_r, Z = sum Z_r
             exp(m_r - M) (kernel mpv_bstat_combine).
   backward  one all_reduce(SUM) of the packed [d fe_out | d fx_out | d r_sqrt_sigma]
             buffer (the local backward kernels write straight into it).
@@ -50,8 +50,8 @@ import torch.distributed as dist
 class CommTimer:
     """Optional timing of the exchange's collectives (bench.py --gpus N).
 
-    While enabled, every collective of SampleShardExchange.combine /
-    reduce_grads is bracketed by CUDA events on the current stream (RCCL makes
+    While enabled, every collective of SampleShardExchange.finalize /
+    reduce_grads / reduce_colsum is bracketed by CUDA events on the current stream (RCCL makes
     that stream wait for the collective, so the pair spans it; for device
     tensors these events are the device-side cost) and by a host clock (gloo
     blocks the host until its collective is done).  Off by default: nothing
@@ -117,7 +117,9 @@ def replica_checksum(tensors):
 
 
 class SampleShardExchange:
-    """Exact cross-rank combine of the per-shard statistics and gradients."""
+    """Exact cross-rank combine of the per-shard statistics and gradients:
+    mpvae_ops.LocalExchange's methods, with collectives."""
+    local = False
 
     def __init__(self, group=None, verify=False):
         self.group = group
@@ -166,40 +168,18 @@ class SampleShardExchange:
 
     def stat_slots(self):
         """(world, this rank's slot) of the packed forward statistics
-        (HipShardBackend.forward_local)."""
+        (mpvae_ops.stat_buffers)."""
         return self.world, dist.get_rank(self.group)
 
-    def combine(self, loc, backend):
-        """Global bstat and colsum from a shard's forward_local output: one
-        all_reduce of the packed [colsum | bstat slots] buffer (two collectives,
-        all_gather + all_reduce, for a backend that does not pack)."""
-        bstat, colsum, packed = loc["bstat"], loc["colsum"], loc.get("packed")
-        if packed is not None:
-            COMM_TIMER.run("combine_all_reduce", packed.device,
-                           lambda: dist.all_reduce(packed, group=self.group))
-            B = bstat.shape[1]
-            slots = packed[colsum.numel():].view(self.world, 6, B)
-            return backend.combine_bstats(slots), colsum
-        parts = [torch.empty_like(bstat) for _ in range(self.world)]
-        COMM_TIMER.run("combine_all_gather", bstat.device,
-                       lambda: dist.all_gather(parts, bstat.contiguous(), group=self.group))
-        bstat_global = backend.combine_bstats(torch.stack(parts))
-        COMM_TIMER.run("combine_all_reduce", colsum.device,
-                       lambda: dist.all_reduce(colsum, group=self.group))
-        return bstat_global, colsum
-
-    def gather_slots(self, loc):
-        """The all-reduced packed buffer as (world, 6, B) bstat slots and the
-        summed colsum, for a backend that combines the slots inside its
-        finalize launch (HipShardBackend.finalize_slots); None without a
-        packed buffer (then combine() is used)."""
-        bstat, colsum, packed = loc["bstat"], loc["colsum"], loc.get("packed")
-        if packed is None:
-            return None
+    def finalize(self, backend, shape, loc, *fin, seed_advance=None):
+        """One all_reduce of forward_local's packed [colsum | bstat slots]
+        buffer; the backend combines the (world, 6, B) slots and finalizes
+        (ShardBackend.finalize_slots: one launch on the GPU)."""
+        packed, colsum = loc["packed"], loc["colsum"]
         COMM_TIMER.run("combine_all_reduce", packed.device,
                        lambda: dist.all_reduce(packed, group=self.group))
-        B = bstat.shape[1]
-        return packed[colsum.numel():].view(self.world, 6, B), colsum
+        slots = packed[colsum.numel():].view(self.world, 6, shape.B)
+        return backend.finalize_slots(shape, slots, colsum, *fin, seed_advance=seed_advance)
 
     def reduce_colsum(self, colsum):
         """predict_proba: the ranks' (B, L) sums over their samples of E_x,

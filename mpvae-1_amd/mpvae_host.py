@@ -9,11 +9,9 @@ fp32 in the reference's op order, fp64 after).  This is a backend for CPU
 tensors, not a fallback: CUDA tensors always run the HIP library and raise
 when it is missing.
 
-``HostShardBackend`` has the per-shard interface of
-``mpvae_ops.HipShardBackend`` (forward_local / combine_bstats / finalize /
-backward_local / kl_backward / predict_local), so ``ProbitELBO``,
-``probit_predict`` and the sample-sharded exchange (mpvae_dist.py, gloo on CPU)
-drive it unchanged.
+``HostShardBackend`` is a ``mpvae_ops.ShardBackend`` (the per-shard interface,
+declared there), so ``ProbitELBO``, ``probit_predict`` and the sample-sharded
+exchange (mpvae_dist.py, gloo on CPU) drive it as they drive the GPU's.
 """
 import ctypes
 import os
@@ -21,6 +19,7 @@ import os
 import torch
 
 import mpvae_hip as H
+from mpvae_ops import ShardBackend, stat_buffers
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MPVAE_HOST_LIB", os.path.join(HERE, "libmpvae_host.so"))
@@ -85,24 +84,15 @@ def _check(rc, what):
         raise H.MPVError(f"{what} failed ({rc}): {load_library().mpvh_last_error().decode()}")
 
 
-def _p(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
 def _c(t, dtype):
     if t.dtype != dtype:
         raise TypeError(f"expected {dtype}, got {t.dtype}")
     return t.detach().contiguous()
 
 
-class HostShardBackend:
-    """Per-shard arithmetic on the CPU through libmpvae_host.so (the interface of
-    mpvae_ops.HipShardBackend; statistics in fp64)."""
-
-    reads_live_slots = True   # gscal may hold just the live TOTAL slot
-
-    def shape(self, S_local, S_total, s_offset, B, L, z):
-        return H.Shape(S_local, S_total, s_offset, B, L, z)
+class HostShardBackend(ShardBackend):
+    """Per-shard arithmetic on the CPU through libmpvae_host.so (statistics in
+    fp64)."""
 
     def make_noise(self, shape, device, seed, offset):
         raise ValueError("args.mpvae_noise = 'philox' draws on the GPU; CPU tensors take the "
@@ -116,26 +106,15 @@ class HostShardBackend:
             raise TypeError(f"r_sqrt_sigma must be float32 or float64 (got {R.dtype})")
         return R.detach().contiguous()
 
-    def from_f32(self, x32, dtype):
-        return x32 if dtype == F32 else x32.to(dtype)
-
     def forward_local(self, shape, y, fe_out, fx_out, Rop, eps, keep_T, stat_slots=None):
         S, B, L = shape.S_local, shape.B, shape.L
         T = torch.empty((S, B, L), dtype=F32) if keep_T else None
         rowstat = torch.empty((6, B, S), dtype=F64)
-        packed = None
-        if stat_slots is None:
-            bstat = torch.empty((6, B), dtype=F64)
-            colsum = torch.empty((2, B, L), dtype=F64)
-        else:  # [colsum | world slots of bstat]: one all_reduce sums and gathers
-            world, slot = stat_slots
-            n = 2 * B * L
-            packed = torch.zeros((n + world * 6 * B,), dtype=F64)
-            colsum = packed[:n].view(2, B, L)
-            bstat = packed[n + slot * 6 * B:n + (slot + 1) * 6 * B].view(6, B)
+        packed, colsum, bstat = stat_buffers(B, L, stat_slots,
+                                             lambda n: torch.empty(n, dtype=F64))
         y, fe_out, fx_out = (_c(t, F32) for t in (y, fe_out, fx_out))
-        a = FwdArgs(_p(y), _p(fe_out), _p(fx_out), _p(Rop), H.F64 if Rop.dtype == F64 else H.F32,
-                    _p(eps), _p(T), _p(rowstat), _p(bstat), _p(colsum))
+        a = FwdArgs(H.ptr(y), H.ptr(fe_out), H.ptr(fx_out), H.ptr(Rop), H.F64 if Rop.dtype == F64 else H.F32,
+                    H.ptr(eps), H.ptr(T), H.ptr(rowstat), H.ptr(bstat), H.ptr(colsum))
         _check(load_library().mpvh_probit_fwd(shape, a), "mpvh_probit_fwd")
         return dict(rowstat=rowstat, bstat=bstat, colsum=colsum, T=T, packed=packed)
 
@@ -146,9 +125,9 @@ class HostShardBackend:
             raise ValueError("args.mpvae_seed_advance is a device-key option (philox on the GPU)")
         colsum = torch.empty((shape.B, shape.L), dtype=F64)
         fx_out = _c(fx_out, F32)
-        _check(load_library().mpvh_probit_predict(shape, _p(fx_out), _p(Rop),
-                                                  H.F64 if Rop.dtype == F64 else H.F32, _p(eps),
-                                                  _p(colsum)), "mpvh_probit_predict")
+        _check(load_library().mpvh_probit_predict(shape, H.ptr(fx_out), H.ptr(Rop),
+                                                  H.F64 if Rop.dtype == F64 else H.F32, H.ptr(eps),
+                                                  H.ptr(colsum)), "mpvh_probit_predict")
         return colsum, (self.indiv_from_colsum(colsum, shape.S_total) if want_indiv else None)
 
     @staticmethod
@@ -159,7 +138,7 @@ class HostShardBackend:
     def combine_bstats(self, gathered):
         g = gathered.to(F64).contiguous()
         out = torch.empty(g.shape[1:], dtype=F64)
-        _check(load_library().mpvh_bstat_combine(_p(g), g.shape[0], g.shape[2], _p(out)),
+        _check(load_library().mpvh_bstat_combine(H.ptr(g), g.shape[0], g.shape[2], H.ptr(out)),
                "mpvh_bstat_combine")
         return out
 
@@ -173,15 +152,13 @@ class HostShardBackend:
         indiv_label = torch.empty((B, L), dtype=F32)
         mus = [_c(t, F32) for t in (fe_mu, fe_logvar, fx_mu, fx_logvar)]
         bstat, colsum = bstat.to(F64).contiguous(), colsum.to(F64).contiguous()
-        a = FinalArgs(_p(bstat), _p(colsum), *[_p(t) for t in mus], fe_mu.shape[1], nll_coeff,
-                      c_coeff, _p(out6), _p(indiv), _p(indiv_label))
+        a = FinalArgs(H.ptr(bstat), H.ptr(colsum), *[H.ptr(t) for t in mus], fe_mu.shape[1], nll_coeff,
+                      c_coeff, H.ptr(out6), H.ptr(indiv), H.ptr(indiv_label))
         _check(load_library().mpvh_probit_finalize(shape, a), "mpvh_probit_finalize")
         return (*[out6[i] for i in range(6)], indiv, indiv_label)
 
     def backward_local(self, shape, saved, gscal, live, g_I, g_IL, nll_coeff, c_coeff, want_dR,
                        dR_dtype=F32, kl=False):
-        """HipShardBackend.backward_local's contract: (flat fp32 [d fe_out | d fx_out
-        | d r_sqrt_sigma], its (2, B, L) view, dR in dR_dtype[, the 4 KL grads])."""
         B, L, z = shape.B, shape.L, shape.z
         d2 = torch.empty((2, B, L), dtype=F64)
         dR64 = torch.empty((L, z), dtype=F64) if want_dR else None
@@ -191,9 +168,9 @@ class HostShardBackend:
         bstat = saved["bstat"].to(F64).contiguous()
         g_I = None if g_I is None else _c(g_I, F32)
         g_IL = None if g_IL is None else _c(g_IL, F32)
-        a = BwdArgs(_p(saved["y"]), _p(saved["fe_out"]), _p(saved["fx_out"]), _p(saved["eps"]),
-                    _p(saved["T"]), _p(rowstat), _p(bstat), _p(gscal), int(live), _p(g_I),
-                    _p(g_IL), nll_coeff, c_coeff, _p(d2), _p(dR64))
+        a = BwdArgs(H.ptr(saved["y"]), H.ptr(saved["fe_out"]), H.ptr(saved["fx_out"]), H.ptr(saved["eps"]),
+                    H.ptr(saved["T"]), H.ptr(rowstat), H.ptr(bstat), H.ptr(gscal), int(live), H.ptr(g_I),
+                    H.ptr(g_IL), nll_coeff, c_coeff, H.ptr(d2), H.ptr(dR64))
         _check(load_library().mpvh_probit_bwd(shape, a), "mpvh_probit_bwd")
         n = 2 * B * L
         local64 = dR_dtype == F64 and want_dR
@@ -217,7 +194,7 @@ class HostShardBackend:
         B, d = fe_mu.shape
         outs = [torch.empty((B, d), dtype=F32) for _ in range(4)]  # g_fe_mu, g_fe_logvar, ...
         g = _c(gscal.reshape(-1).to(F32), F32)
-        _check(load_library().mpvh_kl_bwd(*[_p(t) for t in mus], B, d, _p(g), int(live),
-                                          _p(outs[0]), _p(outs[1]), _p(outs[2]), _p(outs[3])),
+        _check(load_library().mpvh_kl_bwd(*[H.ptr(t) for t in mus], B, d, H.ptr(g), int(live),
+                                          H.ptr(outs[0]), H.ptr(outs[1]), H.ptr(outs[2]), H.ptr(outs[3])),
                "mpvh_kl_bwd")
         return outs

@@ -4,9 +4,11 @@
 one custom Function: its forward launches noise (optional) -> fused GEMM +
 probit decode + row statistics -> combine -> finalize, and its backward the
 analytic gradient kernels.  Sharding of the
-Monte-Carlo axis across ranks plugs in through ``exchange`` (mpvae_dist.py);
-the per-shard arithmetic through ``backend`` (``HipShardBackend`` here -- the
-only backend the product ever uses).
+Monte-Carlo axis across ranks plugs in through ``exchange`` (``LocalExchange``
+here, ``mpvae_dist.SampleShardExchange``: the same methods on both); the
+per-shard arithmetic through ``backend``, a ``ShardBackend`` (the interface,
+declared once below): ``HipShardBackend`` here for CUDA tensors,
+``mpvae_host.HostShardBackend`` for CPU tensors, an oracle one in the tests.
 
 ``FusedReparam`` is the reparameterisation of both encoders in one launch
 (mpvae.py:66-74).
@@ -67,7 +69,114 @@ def eps_cols(shape):
     return int(n)
 
 
-class HipShardBackend:
+def stat_buffers(B, L, stat_slots, alloc):
+    """(packed, colsum (2, B, L), bstat (6, B)): forward_local's statistics
+    buffers from ``alloc(shape)`` (uninitialised storage of the backend's
+    dtype).  stat_slots None: two buffers, packed None.  stat_slots = (world,
+    slot): views of one packed buffer [colsum (2 B L) | world slots of bstat
+    (6 B)], bstat being this shard's slot and the slots zeroed, so that ONE
+    all_reduce(SUM) of it both sums colsum and gathers bstat (x + 0 is exact;
+    SampleShardExchange.finalize)."""
+    if stat_slots is None:
+        return None, alloc((2, B, L)), alloc((6, B))
+    world, slot = stat_slots
+    n, m = 2 * B * L, 6 * B
+    packed = alloc((n + world * m,))
+    packed[n:].zero_()
+    return packed, packed[:n].view(2, B, L), packed[n + slot * m:n + (slot + 1) * m].view(6, B)
+
+
+class ShardBackend:
+    """The per-shard arithmetic ProbitELBO and probit_predict drive: what a
+    backend defines, and the defaults of what it may leave out.  A method a
+    backend does not define raises NotImplementedError.  Subclasses keep every
+    name, parameter order and default (tests/test_backend_interface.py)."""
+
+    def shape(self, S_local, S_total, s_offset, B, L, z):
+        """The problem's sizes as the backend's calls take them: samples
+        [s_offset, s_offset + S_local) of S_total, batch B, labels L, latent z."""
+        return H.Shape(S_local, S_total, s_offset, B, L, z)
+
+    def make_noise(self, shape, device, seed, offset):
+        """Philox noise of this shard, as the GEMM operand.  seed: an int, or a
+        one-element int64 tensor on `device` read at run time."""
+        raise NotImplementedError
+
+    def prepare_noise(self, eps, shape):
+        """Explicit contiguous (S_local, B, z) fp32 noise -> the GEMM operand."""
+        raise NotImplementedError
+
+    def prepare_R(self, R):
+        """r_sqrt_sigma (L, z) fp64 / fp32 -> the GEMM operand (R.T.float(),
+        mpvae.py:165); TypeError for another dtype."""
+        raise NotImplementedError
+
+    def make_noise_and_R(self, shape, device, seed, offset, R):
+        """(make_noise(...), prepare_R(R)); a backend may fuse the two."""
+        return self.make_noise(shape, device, seed, offset), self.prepare_R(R)
+
+    def from_f32(self, x32, dtype):
+        """A summed fp32 gradient in r_sqrt_sigma's dtype."""
+        return x32 if dtype == torch.float32 else x32.to(dtype)
+
+    def forward_local(self, shape, y, fe_out, fx_out, Rop, eps, keep_T, stat_slots=None):
+        """This shard's statistics: dict(rowstat (6, B, S_local), bstat (6, B),
+        colsum (2, B, L), T (what backward_local needs of the forward, None
+        unless keep_T), packed).  stat_slots = exchange.stat_slots(): see
+        stat_buffers for bstat, colsum and packed."""
+        raise NotImplementedError
+
+    def predict_local(self, shape, fx_out, Rop, eps, want_indiv=True, seed_advance=None):
+        """(this shard's (B, L) sum over s of E_x, indiv_prob = that / S_total
+        or None).  want_indiv=False for a sharded caller, which divides after
+        its all-reduce (indiv_from_colsum).  seed_advance: as finalize's."""
+        raise NotImplementedError
+
+    @staticmethod
+    def indiv_from_colsum(colsum, S_total):
+        """indiv_prob from the all-reduced (B, L) column sums, rounded as
+        predict_local rounds its own."""
+        raise NotImplementedError
+
+    def combine_bstats(self, gathered):
+        """The exact combine of the shards' (world, 6, B) bstat: M = max m_r,
+        Z = sum Z_r exp(m_r - M), the ranking sums added."""
+        raise NotImplementedError
+
+    def finalize(self, shape, bstat, colsum, fe_mu, fe_logvar, fx_mu, fx_logvar, nll_coeff,
+                 c_coeff, seed_advance=None):
+        """The 8 outputs from the global statistics.  seed_advance: a device
+        Philox key (int64 tensor) this step's noise has read, advanced by 1 in
+        the same launch; a backend without device keys raises on one."""
+        raise NotImplementedError
+
+    def finalize_slots(self, shape, slots, colsum, fe_mu, fe_logvar, fx_mu, fx_logvar, nll_coeff,
+                       c_coeff, seed_advance=None):
+        """(the combined (6, B) bstat, the 8 outputs) from the all-reduced
+        (world, 6, B) slots of the shards' bstat and the summed colsum."""
+        bstat = self.combine_bstats(slots)
+        return bstat, self.finalize(shape, bstat, colsum, fe_mu, fe_logvar, fx_mu, fx_logvar,
+                                    nll_coeff, c_coeff, seed_advance=seed_advance)
+
+    def backward_local(self, shape, saved, gscal, live, g_I, g_IL, nll_coeff, c_coeff, want_dR,
+                       dR_dtype=torch.float32, kl=False):
+        """(flat, its (2, B, L) view [d fe_out, d fx_out], dR or None[, the 4
+        KL gradients when kl]) of this shard.  flat is the fp32 buffer
+        [d fe_out | d fx_out | d r_sqrt_sigma] the exchange sums over the
+        ranks, dR its tail -- unless dR_dtype is float64: dR is then a tensor
+        of its own, outside flat (no cross-shard sum may follow).  gscal: the
+        upstream gradients of the 6 scalars, or one element when live == 1
+        (the total's alone); live: bit i set when slot i is.  kl: kl_backward
+        on saved's fe_mu ... fx_logvar rides along."""
+        raise NotImplementedError
+
+    def kl_backward(self, fe_mu, fe_logvar, fx_mu, fx_logvar, gscal, live=0x3F):
+        """[g_fe_mu, g_fe_logvar, g_fx_mu, g_fx_logvar]; gscal, live as
+        backward_local's."""
+        raise NotImplementedError
+
+
+class HipShardBackend(ShardBackend):
     """Per-shard arithmetic on the GPU through the C ABI.
 
     gemm="f16x3" (default): the two noise GEMMs run on the f16 matrix cores
@@ -78,9 +187,6 @@ class HipShardBackend:
     (0xFF) before the launch, so a write the kernels skip or lose shows up as a
     NaN instead of hiding behind the identical bytes the caching allocator
     hands back from an earlier launch."""
-
-    # the kernels read only the live upstream-gradient slots (ABI 10)
-    reads_live_slots = True
 
     def __init__(self, gemm="f16x3", poison=False):
         if gemm not in GEMMS:
@@ -93,9 +199,6 @@ class HipShardBackend:
         if self.poison:
             t.view(torch.uint8).fill_(0xFF)  # all-ones words: NaN in fp32 and fp64
         return t
-
-    def shape(self, S_local, S_total, s_offset, B, L, z):
-        return H.Shape(S_local, S_total, s_offset, B, L, z)
 
     @staticmethod
     def _check_seed(seed, device):
@@ -211,11 +314,6 @@ class HipShardBackend:
         return H.ptr(Rop), eps32, H.Split16(), eps16
 
     def forward_local(self, shape, y, fe_out, fx_out, Rop, eps, keep_T, stat_slots=None):
-        """stat_slots = (world, slot): colsum and bstat are written into one
-        packed buffer [colsum (2 B L) | world slots of bstat (6 B)], this
-        shard's bstat into its slot and the other slots zero, so that ONE
-        all_reduce(SUM) of it both sums colsum and gathers bstat (x + 0 is
-        exact); returned as "packed" (SampleShardExchange.combine)."""
         lib = H.load_library()
         dev = y.device
         S, B, L = shape.S_local, shape.B, shape.L
@@ -223,17 +321,7 @@ class HipShardBackend:
         f32 = torch.float32
         T = self._buf((B, S, (L + 3) // 4 * 4), dev, f32) if keep_T else None
         rowstat = self._buf((6, B, S), dev, f32)
-        packed = None
-        if stat_slots is None:
-            bstat = self._buf((6, B), dev, f32)
-            colsum = self._buf((2, B, L), dev, f32)
-        else:
-            world, slot = stat_slots
-            n = 2 * B * L
-            packed = self._buf((n + world * 6 * B,), dev, f32)
-            packed[n:].zero_()
-            colsum = packed[:n].view(2, B, L)
-            bstat = packed[n + slot * 6 * B:n + (slot + 1) * 6 * B].view(6, B)
+        packed, colsum, bstat = stat_buffers(B, L, stat_slots, lambda n: self._buf(n, dev, f32))
         nbytes = lib.mpv_fwd_workspace_bytes(shape)
         ws = self._buf((max(nbytes, 1),), dev, torch.uint8)
         args = H.FwdArgs(H.ptr(y), H.ptr(fe_out), H.ptr(fx_out), self.gemm,
@@ -243,11 +331,8 @@ class HipShardBackend:
         return dict(rowstat=rowstat, bstat=bstat, colsum=colsum, T=T, packed=packed)
 
     def predict_local(self, shape, fx_out, Rop, eps, want_indiv=True, seed_advance=None):
-        """mpv_probit_predict: (this shard's (B, L) sum over s of E_x,
-        indiv_prob = that / S_total or None).  want_indiv=False for a sharded
-        caller, which divides after its all-reduce.  No host sync; the
-        workspace comes from the caching allocator (the graph pool inside a
-        capture)."""
+        """mpv_probit_predict.  No host sync; the workspace comes from the
+        caching allocator (the graph pool inside a capture)."""
         lib = H.load_library()
         dev = fx_out.device
         B, L = shape.B, shape.L
@@ -282,9 +367,7 @@ class HipShardBackend:
 
     def finalize_slots(self, shape, slots, colsum, fe_mu, fe_logvar, fx_mu, fx_logvar, nll_coeff,
                        c_coeff, seed_advance=None):
-        """combine_bstats + finalize in one launch (mpv_probit_finalize_shards):
-        slots is the all-reduced (world, 6, B) buffer of the shards' bstat.
-        Returns (the combined (6, B) bstat, the 8 outputs)."""
+        """combine_bstats + finalize in one launch (mpv_probit_finalize_shards)."""
         B = shape.B
         bstat = torch.empty((6, B), device=colsum.device, dtype=torch.float32)
         fin, outs = self._final_args(shape, None, colsum, fe_mu, fe_logvar, fx_mu, fx_logvar,
@@ -306,8 +389,6 @@ class HipShardBackend:
 
     def finalize(self, shape, bstat, colsum, fe_mu, fe_logvar, fx_mu, fx_logvar, nll_coeff,
                  c_coeff, seed_advance=None):
-        """The 8 outputs; seed_advance: a device Philox key (int64 tensor) this
-        step's noise has read, advanced by 1 in the same launch."""
         args, outs = self._final_args(shape, bstat, colsum, fe_mu, fe_logvar, fx_mu, fx_logvar,
                                       nll_coeff, c_coeff, seed_advance)
         H.check(H.load_library().mpv_probit_finalize(shape, args, H.stream_of(bstat.device)),
@@ -316,10 +397,8 @@ class HipShardBackend:
 
     def backward_local(self, shape, saved, gscal, live, g_I, g_IL, nll_coeff, c_coeff, want_dR,
                        dR_dtype=torch.float32, kl=False):
-        """d fe_out, d fx_out and (want_dR) d r_sqrt_sigma of this shard.
-        dR_dtype float64: dR written in fp64 directly (no cross-shard sum may
-        follow: it is then not part of the packed fp32 buffer).  kl: the KL
-        backward runs in the same call (saved fe_mu ... fx_logvar)."""
+        """One mpv_probit_bwd call: dR_dtype float64 is written in fp64
+        directly, and the KL backward runs in the same call."""
         lib = H.load_library()
         dev = gscal.device
         B, L, z = shape.B, shape.L, shape.z
@@ -365,19 +444,39 @@ class HipShardBackend:
 
 
 class LocalExchange:
-    """Single shard: global statistics are the local ones."""
-    world = 1
+    """Single shard: global statistics are the local ones.
+
+    The exchange interface, which mpvae_dist.SampleShardExchange implements
+    with collectives.  ``local``: no other shard exists, so the backward may
+    write dR in r_sqrt_sigma's own dtype and fuse the KL backward, and predict
+    divides in its own launch; a SampleShardExchange is never local, a world
+    of one included."""
+    world, local = 1, True
+
+    def agree_seed(self, seed, device):
+        """The Philox seed every shard draws from."""
+        return seed
 
     def verify_replicas(self, tensors, names=None):
-        pass
+        """Raise unless every shard holds the same tensors."""
 
     def stat_slots(self):
+        """backend.forward_local's stat_slots: None, or (world, this shard's slot)."""
         return None
 
-    def combine(self, loc, backend):
-        return loc["bstat"], loc["colsum"]
+    def finalize(self, backend, shape, loc, *fin, seed_advance=None):
+        """(the global (6, B) bstat, the 8 outputs) from this shard's
+        forward_local output `loc`; fin = (fe_mu, fe_logvar, fx_mu, fx_logvar,
+        nll_coeff, c_coeff)."""
+        return loc["bstat"], backend.finalize(shape, loc["bstat"], loc["colsum"], *fin,
+                                              seed_advance=seed_advance)
+
+    def reduce_colsum(self, colsum):
+        """predict_local's (B, L) sums, summed over the shards in place."""
+        return colsum
 
     def reduce_grads(self, flat):
+        """backward_local's flat buffer, summed over the shards in place."""
         return flat
 
 
@@ -402,17 +501,13 @@ def _operands(be, cfg, shape, device, R, eps):
     """(eps, Rop): the noise and r_sqrt_sigma as the backend's GEMM operands.
     Philox noise (cfg.noise) is drawn on the device -- a small r_sqrt_sigma's
     split rides on that launch (make_noise_and_R) -- explicit noise is eps."""
-    if cfg.noise == "philox" and hasattr(be, "make_noise_and_R"):
-        return be.make_noise_and_R(shape, device, cfg.seed, cfg.offset, R)
     if cfg.noise == "philox":
-        eps = be.make_noise(shape, device, cfg.seed, cfg.offset)
-    else:
-        eps = _f32(eps, "noise")
-        want = (cfg.S_local, shape.B, shape.z)
-        if tuple(eps.shape) != want:
-            raise ValueError(f"noise must be {want}, got {tuple(eps.shape)}")
-        eps = be.prepare_noise(eps, shape)
-    return eps, be.prepare_R(R)
+        return be.make_noise_and_R(shape, device, cfg.seed, cfg.offset, R)
+    eps = _f32(eps, "noise")
+    want = (cfg.S_local, shape.B, shape.z)
+    if tuple(eps.shape) != want:
+        raise ValueError(f"noise must be {want}, got {tuple(eps.shape)}")
+    return be.prepare_noise(eps, shape), be.prepare_R(R)
 
 
 def probit_predict(fx_out, R, eps, cfg):
@@ -423,21 +518,20 @@ def probit_predict(fx_out, R, eps, cfg):
     all_reduce(SUM) of the (B, L) column sums, then a plain division by
     S_total.  No autograd: the result never has a grad_fn."""
     with torch.no_grad():
-        be = cfg.backend
+        be, ex = cfg.backend, cfg.exchange
         fx_out = _f32(fx_out.detach(), "fx_out")
         B, L = fx_out.shape
         if R.dim() != 2 or R.shape[0] != L:
             raise ValueError(f"r_sqrt_sigma must be (label_dim={L}, z_dim), got {tuple(R.shape)}")
         R = R.detach()
         z = R.shape[1]
-        cfg.exchange.verify_replicas((fx_out, R), names=("fx_out", "r_sqrt_sigma"))
+        ex.verify_replicas((fx_out, R), names=("fx_out", "r_sqrt_sigma"))
         shape = be.shape(cfg.S_local, cfg.S_total, cfg.s_offset, B, L, z)
         eps, Rop = _operands(be, cfg, shape, fx_out.device, R, eps)
-        sharded = hasattr(cfg.exchange, "reduce_colsum")  # SampleShardExchange, not LocalExchange
-        colsum, indiv = be.predict_local(shape, fx_out, Rop, eps, want_indiv=not sharded,
+        colsum, indiv = be.predict_local(shape, fx_out, Rop, eps, want_indiv=ex.local,
                                          seed_advance=cfg.seed_advance)
-        if sharded:
-            indiv = be.indiv_from_colsum(cfg.exchange.reduce_colsum(colsum), cfg.S_total)
+        if not ex.local:
+            indiv = be.indiv_from_colsum(ex.reduce_colsum(colsum), cfg.S_total)
         return indiv
 
 
@@ -463,18 +557,9 @@ class ProbitELBO(torch.autograd.Function):
         need = ctx.needs_input_grad
         keep_T = need[1] or need[4] or need[7]
         fin = (fe_mu, fe_logvar, fx_mu, fx_logvar, cfg.nll_coeff, cfg.c_coeff)
-        adv = {} if cfg.seed_advance is None else {"seed_advance": cfg.seed_advance}
         loc = be.forward_local(shape, y, fe_out, fx_out, Rop, eps, keep_T,
                                stat_slots=cfg.exchange.stat_slots())
-        gathered = (cfg.exchange.gather_slots(loc)
-                    if hasattr(be, "finalize_slots") and hasattr(cfg.exchange, "gather_slots")
-                    else None)
-        if gathered is not None:
-            # sharded: the exact cross-shard combine inside the finalize launch
-            bstat, outs = be.finalize_slots(shape, gathered[0], gathered[1], *fin, **adv)
-        else:
-            bstat, colsum = cfg.exchange.combine(loc, be)
-            outs = be.finalize(shape, bstat, colsum, *fin, **adv)
+        bstat, outs = cfg.exchange.finalize(be, shape, loc, *fin, seed_advance=cfg.seed_advance)
         ctx.set_materialize_grads(False)
         ctx.cfg, ctx.shape, ctx.r_dtype, ctx.keep_T = cfg, shape, R.dtype, keep_T
         ctx.consumed = False
@@ -495,8 +580,8 @@ class ProbitELBO(torch.autograd.Function):
         gs = [g_total, g_nll, g_nll_x, g_c, g_c_x, g_kl]
         live = sum(1 << i for i, g in enumerate(gs) if g is not None)
         dev = sv["y"].device
-        if getattr(be, "reads_live_slots", False) and live == 1:
-            # total_loss.backward() alone: the kernels read only the live slot,
+        if live == 1:
+            # total_loss.backward() alone: a backend reads only the live slot,
             # so the upstream gradient's own storage is gscal (no zeros + stack:
             # two launches fewer per step)
             gscal = gs[0].reshape((1,)).to(torch.float32).contiguous()
@@ -513,9 +598,7 @@ class ProbitELBO(torch.autograd.Function):
             # one shard: dR straight in R's dtype and the KL backward in the
             # same call (two launches fewer); sharded: the packed fp32 buffer
             # is summed over the ranks first
-            local = getattr(cfg.exchange, "world", 1) == 1 and isinstance(cfg.exchange,
-                                                                         LocalExchange)
-            dR_dtype = ctx.r_dtype if local else torch.float32
+            dR_dtype = ctx.r_dtype if cfg.exchange.local else torch.float32
             res = be.backward_local(shape, sv, gscal, live, g_I, g_IL, cfg.nll_coeff,
                                     cfg.c_coeff, need[7], dR_dtype=dR_dtype, kl=want_kl)
             flat, dfe_dfx, dR = res[:3]
@@ -531,8 +614,7 @@ class ProbitELBO(torch.autograd.Function):
         if want_kl:
             if gk is None:
                 gk = be.kl_backward(sv["fe_mu"], sv["fe_logvar"], sv["fx_mu"], sv["fx_logvar"],
-                                    gscal, **({"live": live} if getattr(be, "reads_live_slots",
-                                                                       False) else {}))
+                                    gscal, live)
             grads[2], grads[3], grads[5], grads[6] = gk
         ctx.saved = None
         return tuple(grads)

@@ -477,6 +477,31 @@ def _np():
     return numpy
 
 
+def step_args(args, advance_seed=True):
+    """``args`` for one step's compute_loss or one batch's predict_proba: with a
+    device seed, fresh probit noise every call, on the device -- the finalize
+    (or predict) launch advances the key after the noise has read it
+    (args.mpvae_seed_advance; no launch of its own)."""
+    if advance_seed and isinstance(getattr(args, "mpvae_seed", None), torch.Tensor):
+        args = copy.copy(args)
+        args.mpvae_seed_advance = True
+    return args
+
+
+def _need_device_philox(args, who):
+    """A capture draws its noise on the device, from a key it reads there."""
+    if getattr(args, "mpvae_noise", "torch_cpu") != "philox" or not isinstance(
+            getattr(args, "mpvae_seed", None), torch.Tensor):
+        raise ValueError(f"{who} needs args.mpvae_noise = 'philox' and a one-element int64 "
+                         "device tensor as args.mpvae_seed")
+
+
+def _need_capturable(opt, who):
+    """A captured Adam keeps its step counter and bias corrections on the device."""
+    if not all(g.get("capturable") for g in opt.param_groups):
+        raise ValueError(f"{who} needs torch.optim.Adam(..., fused=True, capturable=True)")
+
+
 _EpochGraph = collections.namedtuple("_EpochGraph", ["graph", "split", "B", "bufs", "out"])
 
 
@@ -563,24 +588,13 @@ class TrainStep:
         for dt, grads in by_dtype.items():
             torch._foreach_mul_(grads, coef.to(dt))
 
-    def _step_args(self):
-        """``args`` for one step's compute_loss: with a device seed, fresh probit
-        noise every step, on the device -- compute_loss's finalize launch
-        advances the key after the noise has read it (args.mpvae_seed_advance;
-        no launch of its own)."""
-        args = self.args
-        if self.advance_seed and isinstance(getattr(args, "mpvae_seed", None), torch.Tensor):
-            args = copy.copy(self.args)
-            args.mpvae_seed_advance = True
-        return args
-
     def _objective(self, label, feat):
         """Forward and loss: ``(the tensor to backpropagate, the step's
         outputs)``.  Here compute_loss's total and its 8 outputs; a subclass
         adds its terms (FairTrainStep)."""
         import mpvae
         out = self.model(label, feat)
-        res = mpvae.compute_loss(label, *out, self.model.r_sqrt_sigma, self._step_args())
+        res = mpvae.compute_loss(label, *out, self.model.r_sqrt_sigma, step_args(self.args, self.advance_seed))
         return res[0], res
 
     def _body(self, label, feat):
@@ -645,8 +659,7 @@ class TrainStep:
         side stream first (they update the model, as any step does).  The
         optimizer must be built with ``capturable=True`` (its step counter and
         bias corrections then live on the device)."""
-        if not all(g.get("capturable") for g in self.opt.param_groups):
-            raise ValueError("capture() needs torch.optim.Adam(..., fused=True, capturable=True)")
+        _need_capturable(self.opt, "capture()")
         self.label, self.feat = label.clone(), feat.clone()
         self.graph, self.out = _warm_capture(lambda: self._body(self.label, self.feat), warmup,
                                              lambda: self.opt.zero_grad(set_to_none=True))
@@ -707,13 +720,8 @@ class TrainStep:
         holds a full batch.  ``capture()`` and ``__call__`` keep their own graph
         and buffers."""
         B = int(batch_size)
-        if not all(g.get("capturable") for g in self.opt.param_groups):
-            raise ValueError("capture_epoch() needs torch.optim.Adam(..., fused=True, "
-                             "capturable=True)")
-        if getattr(self.args, "mpvae_noise", "torch_cpu") != "philox" or not isinstance(
-                getattr(self.args, "mpvae_seed", None), torch.Tensor):
-            raise ValueError("capture_epoch() needs args.mpvae_noise = 'philox' and a one-element "
-                             "int64 device tensor as args.mpvae_seed")
+        _need_capturable(self.opt, "capture_epoch()")
+        _need_device_philox(self.args, "capture_epoch()")
         if split.device.type != "cuda" or split.device != self.params[0].device:
             raise ValueError("capture_epoch() needs a DeviceSplit on the model's GPU")
         if B < 1 or split.n_order < B:
@@ -824,7 +832,7 @@ class CalibrationStep(_SensInput, TrainStep):
         import mpvae
         import mpvae_fair
         self.opt.zero_grad(set_to_none=True)
-        args = self._step_args()
+        args = step_args(self.args, self.advance_seed)
         with torch.no_grad():
             out = self.model(label, feat)
             res = mpvae.compute_loss(label, *out, self.model.r_sqrt_sigma, args)
@@ -925,7 +933,7 @@ class FairTrainStep(_SensInput, TrainStep):
         import mpvae
         import mpvae_fair
         out = self.model(label, feat)
-        res = mpvae.compute_loss(label, *out, self.model.r_sqrt_sigma, self._step_args())
+        res = mpvae.compute_loss(label, *out, self.model.r_sqrt_sigma, step_args(self.args, self.advance_seed))
         fair, contributed = mpvae_fair.fairness_penalty(
             res[7], res[6], label, self.sens, self.tables, norm, self.args.fair_coeff,
             max_groups=self.max_groups, fused=self.fused)
@@ -1074,17 +1082,10 @@ class EvalPass:
         self.graph = None
         self.label = self.feat = self.out = None
 
-    def _batch_args(self):
-        args = self.args
-        if isinstance(getattr(args, "mpvae_seed", None), torch.Tensor):
-            args = copy.copy(args)
-            args.mpvae_seed_advance = True
-        return args
-
     def _batch(self, label, feat):
         """indiv_prob (B, L) of one batch."""
         import mpvae
-        args = self._batch_args()
+        args = step_args(self.args)
         if self.label_free:
             return self.model.predict_proba(feat, args)
         out = self.model(label, feat)
@@ -1144,10 +1145,7 @@ class EvalPass:
         ``args.mpvae_seed``, TrainStep.capture's conditions: any other noise
         source is drawn on the host."""
         B = self.batch_size
-        if getattr(self.args, "mpvae_noise", "torch_cpu") != "philox" or not isinstance(
-                getattr(self.args, "mpvae_seed", None), torch.Tensor):
-            raise ValueError("capture() needs args.mpvae_noise = 'philox' and a one-element int64 "
-                             "device tensor as args.mpvae_seed")
+        _need_device_philox(self.args, "capture()")
         if labels.shape[0] < B:
             raise ValueError(f"capture() needs a full batch of {B} rows (got {labels.shape[0]})")
         was_training = self.model.training
