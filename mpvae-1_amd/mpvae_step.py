@@ -24,6 +24,7 @@ The loop bodies themselves are one call each (``TrainStep``, ``FairTrainStep``,
 ``torch.from_numpy(data[idx]).float().to(device)``.
 """
 import collections
+import contextlib
 import copy
 import ctypes
 import functools
@@ -265,6 +266,45 @@ def _warm_capture(body, warmup, prepare=None):
     return graph, out
 
 
+class _Captured:
+    """One captured HIP graph: ``graph``, the static input buffers ``bufs`` it
+    reads and ``out``, what the captured run of ``body(*bufs)`` returned (see
+    ``_warm_capture``).  An epoch's record also names its ``split`` and ``B``."""
+
+    def __init__(self, body, bufs, warmup, prepare=None, split=None, B=None):
+        self.bufs, self.split, self.B = list(bufs), split, B
+        self.graph, self.out = _warm_capture(lambda: body(*self.bufs), warmup, prepare)
+
+    def replay(self, *batch):
+        """Copy ``batch`` into the static buffers (an epoch's gather fills them
+        inside the graph: no batch), replay, and return the static outputs."""
+        for buf, x in zip(self.bufs, batch):
+            buf.copy_(x)
+        self.graph.replay()
+        return self.out
+
+
+class _Capturing:
+    """``graph`` and ``out`` of the object's captured record ``_captured`` (None
+    until ``capture()``)."""
+
+    _captured = None
+    graph = property(lambda self: self._captured and self._captured.graph)
+    out = property(lambda self: self._captured and self._captured.out)
+
+
+@contextlib.contextmanager
+def _eval_mode(model):
+    """``model.eval()`` under ``no_grad``; the previous mode is restored."""
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            yield
+    finally:
+        model.train(was_training)
+
+
 _SPLIT_ELEMS = {torch.float32: 0, torch.float64: 1, torch.int32: 2, torch.int64: 3,
                 torch.uint8: 4}  # dtype -> mpv_elem
 
@@ -502,10 +542,7 @@ def _need_capturable(opt, who):
         raise ValueError(f"{who} needs torch.optim.Adam(..., fused=True, capturable=True)")
 
 
-_EpochGraph = collections.namedtuple("_EpochGraph", ["graph", "split", "B", "bufs", "out"])
-
-
-class TrainStep:
+class TrainStep(_Capturing):
     """The loop body of fairsoft_train.py:47-146 (penalty-free) as one call:
     ``model(label, feat)`` -> ``compute_loss`` -> ``backward`` ->
     ``clip_grad_norm_(10)`` -> finite-gradient gate -> optimizer step.
@@ -521,11 +558,19 @@ class TrainStep:
     state back to the host objects).  With ``args.mpvae_noise = "philox"`` and
     a device-tensor ``args.mpvae_seed`` nothing in the step waits for the
     host, so ``capture()`` records it in one HIP graph (input batches are
-    copied into the static ``label`` / ``feat`` buffers before each
-    ``replay()``)."""
+    copied into its static buffers before each replay).
+
+    The batch is the step's argument list: ``inputs`` names the tensors that
+    ``__call__`` / ``step``, ``capture``, ``_body`` and ``_objective`` take, in
+    order, and that ``run_epoch`` gathers from a ``DeviceSplit``; a subclass
+    with a third input declares it there and writes ``_body(self, label, feat,
+    sens)``.  ``params`` (default: the model's trainable parameters) are the
+    tensors the optimizer steps."""
+
+    inputs = ("label", "feat")
 
     def __init__(self, model, optimizer, args, max_grad_norm=10.0, advance_seed=True,
-                 native_adam=True, scheduler=None):
+                 native_adam=True, scheduler=None, params=None):
         if not optimizer.defaults.get("fused"):
             raise ValueError("TrainStep gates the update on the device: use a fused optimizer "
                              "(torch.optim.Adam(..., fused=True))")
@@ -534,8 +579,13 @@ class TrainStep:
         self.advance_seed = advance_seed
         # a plain fused Adam steps in mpv_adam_step (adam_step); others in torch
         self.native_adam = bool(native_adam) and _native_adam(optimizer)
-        self.params = [p for p in model.parameters() if p.requires_grad]
-        self._init_state()
+        self.params = [p for p in model.parameters() if p.requires_grad] \
+            if params is None else list(params)
+        dev = self.params[0].device
+        self.updates = torch.zeros((), dtype=torch.int64, device=dev)  # applied updates
+        self.found_inf = torch.zeros((), dtype=torch.float32, device=dev)  # the gate's flag
+        self._one = torch.ones((), dtype=torch.float32, device=dev)
+        self._drop_graphs()
         self.sched = None
         if scheduler is not None:
             if not self.native_adam:
@@ -543,16 +593,9 @@ class TrainStep:
                                  "torch.optim.Adam with a float lr)")
             self.sched = DeviceStepLR(scheduler, optimizer)
 
-    def _init_state(self):
-        """The step's device state, on ``self.params``' device: the applied-update
-        count, the gate's flag, and no captured graph yet."""
-        dev = self.params[0].device
-        self.updates = torch.zeros((), dtype=torch.int64, device=dev)
-        self.found_inf = torch.zeros((), dtype=torch.float32, device=dev)
-        self._one = torch.ones((), dtype=torch.float32, device=dev)
-        self.graph = None
-        self.label = self.feat = self.out = None
-        self._epoch = None  # capture_epoch's graph and static buffers
+    def _drop_graphs(self):
+        """No captured record: ``_captured`` is capture()'s, ``_epoch`` capture_epoch's."""
+        self._captured = self._epoch = None
 
     def _grads_by_dtype(self):
         """``self.params``' gradients, one list per dtype (fp32 MLP grads, the
@@ -597,14 +640,19 @@ class TrainStep:
         res = mpvae.compute_loss(label, *out, self.model.r_sqrt_sigma, step_args(self.args, self.advance_seed))
         return res[0], res
 
-    def _body(self, label, feat):
+    def _body(self, *batch):
         self.opt.zero_grad(set_to_none=True)
-        objective, res = self._objective(label, feat)
+        objective, res = self._objective(*batch)
         objective.backward()
         self._clip()
-        # finite gate: the AMP multi-tensor check (one launch per dtype) sets
-        # found_inf if any gradient holds a NaN / inf; its unscale by 1.0
-        # leaves every value as it is
+        self._gated_update()
+        return res
+
+    def _gated_update(self):
+        """The finite-gradient gate and the optimizer step it gates, after a
+        backward: the AMP multi-tensor check (one launch per dtype) sets
+        found_inf if any gradient holds a NaN / inf; its unscale by 1.0 leaves
+        every value as it is."""
         self.found_inf.zero_()
         for grads in self._grads_by_dtype().values():
             torch._amp_foreach_non_finite_check_and_unscale_(grads, self.found_inf, self._one)
@@ -620,7 +668,6 @@ class TrainStep:
             finally:
                 del self.opt.found_inf
             self.updates.add_(1 - self.found_inf.to(torch.int64))
-        return res
 
     def sync_scheduler(self):
         """The device StepLR's learning rates written back into the optimizer's
@@ -630,51 +677,50 @@ class TrainStep:
     def release_scheduler(self):
         """Sync and give the StepLR back to host control (its step() works
         again); TrainStep then no longer steps it.  A graph captured before
-        holds the device lr / epoch and the scheduler step in its Adam launches
-        (ADVICE r05): it is dropped, so later calls run eagerly on the host lr
-        until capture() records the step again."""
+        holds the device lr / epoch and the scheduler step in its Adam
+        launches: every captured record is dropped, so later calls run eagerly
+        on the host lr until capture() records the step again."""
         if self.sched is None:
             return None
         lrs, self.sched = self.sched.release(), None
-        self._epoch = None
-        if self.graph is not None:
-            self.graph = None
-            self.label = self.feat = self.out = None
+        self._drop_graphs()
         return lrs
 
-    def __call__(self, label, feat):
-        """One eager step; returns compute_loss's 8 outputs (device tensors)."""
+    def _check_batch(self, batch):
+        if len(batch) != len(self.inputs):
+            raise TypeError(f"{type(self).__name__} takes ({', '.join(self.inputs)}): "
+                            f"{len(self.inputs)} tensors, got {len(batch)}")
+
+    def __call__(self, *batch):
+        """One step on the batch (``inputs``), a replay once captured; returns the
+        step's outputs (here compute_loss's 8, device tensors)."""
+        self._check_batch(batch)
         if self.sched is not None:
             self.sched.adopt_host_lr()
-        if self.graph is not None:
-            self.label.copy_(label)
-            self.feat.copy_(feat)
-            self.graph.replay()
-            return self.out
-        return self._body(label, feat)
+        if self._captured is not None:
+            return self._captured.replay(*batch)
+        return self._body(*batch)
 
-    def capture(self, label, feat, warmup=2):
-        """Record the step in a HIP graph on static copies of (label, feat);
-        later calls copy their batch in and replay.  ``warmup`` eager steps on a
-        side stream first (they update the model, as any step does).  The
-        optimizer must be built with ``capturable=True`` (its step counter and
-        bias corrections then live on the device)."""
+    step = __call__
+
+    def capture(self, *batch, warmup=2):
+        """Record the step in a HIP graph on static copies of the batch; later
+        calls copy their batch in and replay.  ``warmup`` eager steps on a side
+        stream first (they update the model, as any step does).  The optimizer
+        must be built with ``capturable=True`` (its step counter and bias
+        corrections then live on the device)."""
+        self._check_batch(batch)
         _need_capturable(self.opt, "capture()")
-        self.label, self.feat = label.clone(), feat.clone()
-        self.graph, self.out = _warm_capture(lambda: self._body(self.label, self.feat), warmup,
-                                             lambda: self.opt.zero_grad(set_to_none=True))
+        self._captured = _Captured(self._body, [t.clone() for t in batch], warmup,
+                                   lambda: self.opt.zero_grad(set_to_none=True))
         return self.graph
 
     # ---------------------------------------------------------------- epochs
-    _epoch_sens = False  # the step reads the batch's sensitive features (_SensInput)
-
-    def _epoch_body(self, label, feat, sens):
-        """``_body`` on a gathered batch."""
-        return self._body(label, feat)
-
-    def _epoch_step(self, split, B):
-        """Gather the next B rows of the split's order at its cursor, then the step."""
-        return self._epoch_body(*split.next_batch(B, sens=self._epoch_sens))
+    def _next_batch(self, split, B, **kw):
+        """The step's ``inputs`` of the next B rows of the split's order, gathered
+        at its cursor."""
+        n = len(self.inputs)
+        return split.next_batch(B, sens=n > 2, **kw)[:n]
 
     def run_epoch(self, split, order, batch_size):
         """One epoch of the reference's loop (fairsoft_train.py:47-56) over a
@@ -691,20 +737,18 @@ class TrainStep:
         Returns the number of steps; no host sync (``read_totals()`` /
         ``split.check()`` are the caller's)."""
         B = int(batch_size)
-        if B < 1:
-            raise ValueError(f"batch_size must be >= 1 (got {batch_size})")
         full, tail = epoch_batches(split.set_order(order), B)
         if self.sched is not None:
             self.sched.adopt_host_lr()
         ep = self._epoch
         if ep is not None and ep.split is split and ep.B == B:
             for _ in range(full):
-                ep.graph.replay()
+                ep.replay()
         else:
             for _ in range(full):
-                self._epoch_step(split, B)
+                self._body(*self._next_batch(split, B))
         if tail:
-            self._epoch_body(*split.next_batch(tail, advance=False, sens=self._epoch_sens))
+            self._body(*self._next_batch(split, tail, advance=False))
         return full + (1 if tail else 0)
 
     def capture_epoch(self, split, batch_size, warmup=2):
@@ -728,60 +772,24 @@ class TrainStep:
             raise ValueError(f"capture_epoch() needs a full batch of {B} rows in the split's "
                              f"current order (it holds {split.n_order})")
         bufs = [torch.empty((B, t.shape[1]), dtype=dt, device=split.device)
-                for t, dt in split._sources(self._epoch_sens)]
+                for t, dt in split._sources(len(self.inputs) > 2)]
         warming = [True]
 
-        def body():
+        def body(*bufs):
             if warming[0]:
                 split.cursor.zero_()
-            return self._epoch_body(*split.next_batch(B, out=bufs, sens=self._epoch_sens))
+            return self._body(*self._next_batch(split, B, out=bufs))
 
         def prepare():
             warming[0] = False
             self.opt.zero_grad(set_to_none=True)
 
-        graph, out = _warm_capture(body, warmup, prepare)
+        self._epoch = _Captured(body, bufs, warmup, prepare, split, B)
         split.cursor.zero_()
-        self._epoch = _EpochGraph(graph, split, B, bufs, out)
-        return graph
+        return self._epoch.graph
 
 
-class _SensInput:
-    """The batch's sensitive features as the third input of a TrainStep subclass
-    (listed before TrainStep among its bases): ``self.sens`` is the batch's own
-    tensor on an eager step and a third static buffer once captured."""
-
-    sens = None
-
-    def __call__(self, label, feat, sensitive_feat):
-        """One step (a replay once captured) on the batch."""
-        if self.graph is not None:
-            self.sens.copy_(sensitive_feat)
-        else:
-            self.sens = sensitive_feat
-        return super().__call__(label, feat)
-
-    step = __call__
-
-    def capture(self, label, feat, sensitive_feat, warmup=2):
-        """TrainStep.capture with the batch's sensitive features as a third
-        static buffer."""
-        self.sens = sensitive_feat.clone()
-        return super().capture(label, feat, warmup)
-
-    _epoch_sens = True  # run_epoch gathers the sensitive features as a third source
-
-    def _epoch_body(self, label, feat, sens):
-        """``_body`` with the gathered sensitive features; ``self.sens`` (the
-        static buffer of a captured ``step``) is put back afterwards."""
-        kept, self.sens = self.sens, sens
-        try:
-            return self._body(label, feat)
-        finally:
-            self.sens = kept
-
-
-class CalibrationStep(_SensInput, TrainStep):
+class CalibrationStep(TrainStep):
     """The loop body of postprocess_threshold_one_epoch
     (fairsoft_train_postprocess.py:84-175) as one call: the frozen model's
     ``model(label, feat)`` -> ``compute_loss`` (for ``indiv_prob``) ->
@@ -815,20 +823,18 @@ class CalibrationStep(_SensInput, TrainStep):
     ``capture()``; ``scheduler`` is the reference's StepLR or None.  With Philox
     noise and a device seed nothing waits for the host."""
 
+    inputs = ("label", "feat", "sensitive_feat")
+
     def __init__(self, model, threshold_, optimizer, args, tables, centroids, scheduler=None):
         if not _native_adam(optimizer):
             raise ValueError("CalibrationStep steps a plain fused Adam on the device: use "
                              "torch.optim.Adam([threshold_], ..., fused=True) with a float lr")
         if not (threshold_.is_leaf and threshold_.requires_grad):
             raise ValueError("threshold_ must be a leaf tensor that requires a gradient")
-        self.model, self.opt, self.args = model.eval(), optimizer, args
+        super().__init__(model.eval(), optimizer, args, scheduler=scheduler, params=[threshold_])
         self.threshold_, self.tables, self.centroids = threshold_, tables, centroids
-        self.advance_seed, self.native_adam = True, True
-        self.params = [threshold_]
-        self._init_state()
-        self.sched = None if scheduler is None else DeviceStepLR(scheduler, optimizer)
 
-    def _body(self, label, feat):
+    def _body(self, label, feat, sens):
         import mpvae
         import mpvae_fair
         self.opt.zero_grad(set_to_none=True)
@@ -837,15 +843,11 @@ class CalibrationStep(_SensInput, TrainStep):
             out = self.model(label, feat)
             res = mpvae.compute_loss(label, *out, self.model.r_sqrt_sigma, args)
         bce, fair, cal_prob, active, contributed = mpvae_fair.calibration_loss(
-            res[6], self.threshold_, label, self.sens, self.centroids, self.tables,
-            args.learn_logit)
+            res[6], self.threshold_, label, sens, self.centroids, self.tables, args.learn_logit)
         cal_total = fair * args.fair_coeff + bce
         total = torch.where(active, cal_total.detach(), res[0].to(cal_total.dtype))
         (cal_total * active.to(cal_total.dtype)).backward()
-        self.found_inf.zero_()
-        torch._amp_foreach_non_finite_check_and_unscale_([self.threshold_.grad], self.found_inf,
-                                                         self._one)
-        adam_step(self.opt, self.found_inf, self.updates, self.sched)
+        self._gated_update()  # no clip, as the reference
         return total, bce.detach(), fair.detach(), cal_prob, contributed
 
 
@@ -879,7 +881,7 @@ class _Totals:
         self.counts.zero_()
 
 
-class FairTrainStep(_SensInput, TrainStep):
+class FairTrainStep(TrainStep):
     """The loop body of train_mpvae_softfair_one_epoch with ``penalize_unfair``
     (fairsoft_train.py:47-162) as one call: TrainStep's step with the fairness
     regulariser in the objective -- ``model(label, feat)`` -> ``compute_loss``
@@ -920,6 +922,7 @@ class FairTrainStep(_SensInput, TrainStep):
     # fairness_penalty's flag; False (set on an instance before capture) is the
     # unfused penalty, bit for bit the same step: tools/bench_fair_step.py's yardstick
     fused = True
+    inputs = ("label", "feat", "sensitive_feat")
 
     def __init__(self, model, optimizer, args, tables, max_groups=None, scheduler=None):
         super().__init__(model, optimizer, args, scheduler=scheduler)
@@ -927,7 +930,7 @@ class FairTrainStep(_SensInput, TrainStep):
         dev = self.params[0].device
         self.totals, self.valid_totals = _Totals(dev), _Totals(dev)
 
-    def _forward(self, label, feat, norm):
+    def _forward(self, label, feat, sens, norm):
         """Forward, loss, penalty: (the unrounded total + fairloss, a
         FairStepOut without its metrics)."""
         import mpvae
@@ -935,7 +938,7 @@ class FairTrainStep(_SensInput, TrainStep):
         out = self.model(label, feat)
         res = mpvae.compute_loss(label, *out, self.model.r_sqrt_sigma, step_args(self.args, self.advance_seed))
         fair, contributed = mpvae_fair.fairness_penalty(
-            res[7], res[6], label, self.sens, self.tables, norm, self.args.fair_coeff,
+            res[7], res[6], label, sens, self.tables, norm, self.args.fair_coeff,
             max_groups=self.max_groups, fused=self.fused)
         objective = res[0].to(torch.float64) + fair
         if self.tables and self.max_groups is not None:
@@ -955,11 +958,11 @@ class FairTrainStep(_SensInput, TrainStep):
         totals.add(out)
         return out
 
-    def _objective(self, label, feat):
-        return self._forward(label, feat, self.args.fairness_loss_norm)
+    def _objective(self, label, feat, sens):
+        return self._forward(label, feat, sens, self.args.fairness_loss_norm)
 
-    def _body(self, label, feat):
-        return self._with_metrics(super()._body(label, feat), label, self.totals)
+    def _body(self, label, feat, sens):
+        return self._with_metrics(super()._body(label, feat, sens), label, self.totals)
 
     def validate(self, label, feat, sensitive_feat):
         """The loop body of validate_mpvae_softfair (fairsoft_train.py:234-331)
@@ -969,16 +972,9 @@ class FairTrainStep(_SensInput, TrainStep):
         always squares (:305-308), whatever ``fairness_loss_norm`` says, so
         the norm here is "l2".  The model's train / eval mode is restored.
         Runs eagerly: it is not part of a captured graph."""
-        was_training, sens = self.model.training, self.sens
-        self.model.eval()
-        self.sens = sensitive_feat
-        try:
-            with torch.no_grad():
-                _, out = self._forward(label, feat, "l2")
-                return self._with_metrics(out, label, self.valid_totals)
-        finally:
-            self.sens = sens
-            self.model.train(was_training)
+        with _eval_mode(self.model):
+            _, out = self._forward(label, feat, sensitive_feat, "l2")
+            return self._with_metrics(out, label, self.valid_totals)
 
     def validate_epoch(self, split, order, batch_size):
         """validate_mpvae_softfair's loop (fairsoft_train.py:233-331) over a
@@ -987,8 +983,6 @@ class FairTrainStep(_SensInput, TrainStep):
         at the split's cursor; eager.  The sums go to ``valid_totals``; returns
         the number of batches, no host sync."""
         B = int(batch_size)
-        if B < 1:
-            raise ValueError(f"batch_size must be >= 1 (got {batch_size})")
         full, tail = epoch_batches(split.set_order(order), B)
         for _ in range(full):
             self.validate(*split.next_batch(B))
@@ -1022,7 +1016,7 @@ class FairTrainStep(_SensInput, TrainStep):
 EvalOut = collections.namedtuple("EvalOut", ["indiv_prob", "scores"])
 
 
-class EvalPass:
+class EvalPass(_Capturing):
     """fairsoft_evaluate.evaluate_mpvae's loop and scoring (:40-123) over one
     split as one call, on the model's device: the model's ``indiv_prob`` of
     every batch written into one preallocated (N, L) fp32 buffer (what
@@ -1079,8 +1073,6 @@ class EvalPass:
         self.tables = None if tables is None else list(tables)
         self.definitions = None if definitions is None else [list(d) for d in definitions]
         self.centroids, self.label_free, self.slices = centroids, bool(label_free), slices
-        self.graph = None
-        self.label = self.feat = self.out = None
 
     def _batch(self, label, feat):
         """indiv_prob (B, L) of one batch."""
@@ -1097,31 +1089,22 @@ class EvalPass:
             raise ValueError("EvalPass with tables needs the split's sensitive_feat")
         N, L = labels.shape
         B = self.batch_size
-        was_training = self.model.training
-        self.model.eval()
-        try:
-            with torch.no_grad():
-                buf = torch.empty((N, L), dtype=torch.float32, device=feats.device)
-                for i in range(N // B + 1):
-                    s, e = i * B, min((i + 1) * B, N)
-                    if e <= s:
-                        continue
-                    if self.graph is not None and e - s == B:
-                        self.label.copy_(labels[s:e])
-                        self.feat.copy_(feats[s:e])
-                        self.graph.replay()
-                        buf[s:e].copy_(self.out)
-                    else:
-                        buf[s:e].copy_(self._batch(labels[s:e].float(), feats[s:e]))
-                if self.definitions is not None:
-                    scores = mpvae_fair.split_scores_defs(buf, labels, sensitive_feat,
-                                                          self.centroids, self.definitions,
-                                                          weight_labels, self.slices)
+        full, tail = epoch_batches(N, B)
+        with _eval_mode(self.model):
+            buf = torch.empty((N, L), dtype=torch.float32, device=feats.device)
+            for i in range(full + bool(tail)):
+                rows = slice(i * B, min((i + 1) * B, N))
+                if self._captured is not None and i < full:
+                    prob = self._captured.replay(labels[rows], feats[rows])
                 else:
-                    scores = mpvae_fair.split_scores(buf, labels, sensitive_feat, self.centroids,
-                                                     self.tables, weight_labels, self.slices)
-        finally:
-            self.model.train(was_training)
+                    prob = self._batch(labels[rows].float(), feats[rows])
+                buf[rows].copy_(prob)
+            if self.definitions is not None:
+                scores = mpvae_fair.split_scores_defs(buf, labels, sensitive_feat, self.centroids,
+                                                      self.definitions, weight_labels, self.slices)
+            else:
+                scores = mpvae_fair.split_scores(buf, labels, sensitive_feat, self.centroids,
+                                                 self.tables, weight_labels, self.slices)
         return EvalOut(buf, scores)
 
     def run_split(self, split, order=None, weight_labels=None):
@@ -1148,15 +1131,9 @@ class EvalPass:
         _need_device_philox(self.args, "capture()")
         if labels.shape[0] < B:
             raise ValueError(f"capture() needs a full batch of {B} rows (got {labels.shape[0]})")
-        was_training = self.model.training
-        self.model.eval()
-        try:
-            with torch.no_grad():
-                self.label, self.feat = labels[:B].float().clone(), feats[:B].clone()
-                self.graph, self.out = _warm_capture(lambda: self._batch(self.label, self.feat),
-                                                     warmup)
-        finally:
-            self.model.train(was_training)
+        with _eval_mode(self.model):
+            self._captured = _Captured(self._batch, [labels[:B].float().clone(), feats[:B].clone()],
+                                       warmup)
         return self.graph
 
     @staticmethod

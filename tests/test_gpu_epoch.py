@@ -1,5 +1,5 @@
 """GPU: whole epochs fed on the device -- ``TrainStep.run_epoch`` /
-``capture_epoch`` (and FairTrainStep, CalibrationStep through ``_SensInput``),
+``capture_epoch`` (and FairTrainStep, CalibrationStep with their third input),
 ``FairTrainStep.validate_epoch`` and ``EvalPass.run_split`` over a
 ``mpvae_step.DeviceSplit`` -- against the same loops fed by hand, the way the
 reference feeds them: ``torch.from_numpy(data[idx]).float().to(device)``."""
@@ -233,8 +233,7 @@ def test_replayed_epoch_step_has_no_batch_copy():
     torch.cuda.synchronize()
     ours = _device_events(tg._epoch.graph.replay)
     theirs = _device_events(lambda: hand(*batch))
-    feed = _device_events(lambda: (hand.label.copy_(batch[0]), hand.feat.copy_(batch[1]),
-                                   hand.sens.copy_(batch[2])))
+    feed = _device_events(lambda: [buf.copy_(x) for buf, x in zip(hand._captured.bufs, batch)])
     gathers = sum(c for k, c in ours.items() if "gather_" in k)
     print("epoch step:", sum(ours.values()), "device activities,", gathers, "of the gather entry;",
           "hand-fed step:", sum(theirs.values()), "; its three copy_:", feed)

@@ -106,7 +106,7 @@ def feeds(sh, data):
             if e - s == B:
                 step_a(*batch)
             else:  # a captured step has one batch size: the ragged batch runs eagerly
-                step_a._epoch_body(*batch)
+                step_a._body(*batch)
             k += 1
         return k
     out["a_host_fed"] = (epoch_a, lambda: step_a(*host(first)))
@@ -127,7 +127,7 @@ def feeds(sh, data):
             if e - s == B:
                 step_b(*batch)
             else:
-                step_b._epoch_body(*batch)
+                step_b._body(*batch)
             k += 1
         return k
     idx0 = torch.from_numpy(first).to(DEV)
