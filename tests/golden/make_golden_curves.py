@@ -13,8 +13,10 @@ arrays; the fixtures keep length L with NaN in that place (one-class labels:
 roc_auc_score raises or returns NaN depending on the scikit-learn version; both
 mean "undefined").
 
-Usage:  PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden_curves.py
-Writes: tests/golden/curves_*.npz
+Usage:  PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden_curves.py [NAME ...]
+Writes: tests/golden/curves_*.npz, or only the named records (the inputs of
+every record are drawn either way, so a record's bytes do not depend on which
+others are written).
 """
 import importlib.util
 import os
@@ -52,7 +54,12 @@ def per_label(ev, pred, target):
     return out
 
 
+ONLY = set(sys.argv[1:])
+
+
 def record(ev, name, pred, target, sweep=False):
+    if ONLY and name not in ONLY:
+        return
     pred, target = pred.astype(np.float32), target.astype(np.float32)
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
@@ -121,6 +128,33 @@ def main():
         t[1, 0] = 1
         p = (0.02 + 0.96 * rng.random((N, L)) * (0.5 + 0.5 * t)).astype(np.float32)
         record(ev, name, p, t, sweep=True)
+    # The records below draw from a generator of their own.  They cross one
+    # merge and one pass tile of csrc/curves.hip (1024 keys) with scores the
+    # records above do not hold.
+    rng = np.random.default_rng(4102)
+    fmax, tiny = np.finfo(np.float32).max, np.float32(2.0 ** -149)
+    # c6: signed scores with +-0, denormals and +-FLT_MAX; a constant column;
+    # two long runs; all-distinct negative scores
+    N = 1100
+    t = (rng.random((N, 4)) < 0.3).astype(np.float32)
+    p = np.empty((N, 4), np.float32)
+    p[:, 0] = ((rng.random(N) - 0.5) * (1 + t[:, 0] * rng.random(N))).astype(np.float32)
+    edge = np.array([0.0, -0.0, tiny, -tiny, 3 * tiny, -3 * tiny, np.finfo(np.float32).tiny,
+                     fmax, -fmax], np.float32)
+    rows = rng.permutation(N)[:4 * edge.size]
+    p[rows, 0] = np.tile(edge, 4)
+    p[:, 1] = -0.625
+    p[:, 2] = np.where(rng.permutation(N) < 500, 0.25, -0.25)
+    p[:, 3] = (-0.01 - rng.random(N) - 0.5 * (1 - t[:, 3]) * rng.random(N)).astype(np.float32)
+    assert np.unique(p[:, 3]).size == N and (p[:, 3] < 0).all()
+    assert (np.signbit(p[:, 0]) & (t[:, 0] == 1)).any() and (p[:, 0] > 0).any()
+    record(ev, "c6", p, t)
+    # c7: all-distinct signed scores
+    N = 1030
+    t = (rng.random((N, 2)) < 0.3).astype(np.float32)
+    p = ((rng.random((N, 2)) - 0.5) + 0.4 * t * rng.random((N, 2))).astype(np.float32)
+    assert all(np.unique(p[:, l]).size == N for l in range(2))
+    record(ev, "c7", p, t)
 
 
 if __name__ == "__main__":

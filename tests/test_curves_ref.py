@@ -16,7 +16,8 @@ FIX = curve_fixtures()
 
 
 def test_the_fixture_set_is_complete():
-    assert sorted(f["name"] for f in FIX) == ["c1", "c2", "c3", "c4", "c5", "s1", "s2"]
+    assert sorted(f["name"] for f in FIX) == ["c1", "c2", "c3", "c4", "c5", "c6", "c7", "s1",
+                                               "s2"]
     assert mf.THRESHOLDS == cr.THRESHOLDS and len(mf.THRESHOLDS) == 27
     assert mf.METRICS == cr.METRICS and len(mf.METRICS) == 14
 

@@ -159,6 +159,36 @@ def test_nan_score_and_tied_rows():
     _check_loop(_sweep(p, t, THR29), _loop(p, t, THR29))
 
 
+def test_signed_scores_and_a_negative_threshold():
+    """Scores on both sides of zero: the negative branch of sweep_rank_key's
+    sign mapping orders p@k; the threshold -0.25 cuts among them."""
+    N, L = 67, 38
+    rng = np.random.default_rng(7 * N + L + 1)
+    t = (rng.random((N, L)) < 0.3).astype(np.float32)
+    p = (rng.random((N, L)) * 0.5 + 0.3 * t * rng.random((N, L)) - 0.5).astype(np.float32)
+    above = (p > 0).sum(1)
+    print("rows by scores above zero", np.bincount(above))
+    # the best five of most rows hold scores of both signs
+    assert ((above > 0) & (above < 5)).sum() > N // 2 and (above >= 5).any()
+    thr = THR29 + [-0.25]
+    got = _sweep(p, t, thr)
+    _check_oracle(got, _oracle(p, t, thr))
+    _check_loop(got, _loop(p, t, thr))
+
+
+def test_a_row_of_signed_zeros_is_one_tie():
+    """-0.0 and +0.0 in alternation tie, so the row ranks its larger indices
+    first, where the positives are; +0.0 ahead of -0.0 would pick indices 7, 5,
+    3 and miss two of them.  Against the device loop: the tie order is this
+    project's, not the oracle's."""
+    p, t = _seeded(7, 9, 32, 3)
+    p[5, :] = 0.0
+    p[5, ::2] = -0.0
+    t[5] = [0, 0, 0, 0, 0, 0, 1, 1, 1]
+    assert list(np.signbit(p[5])) == [True, False] * 4 + [True]
+    _check_loop(_sweep(p, t, THR29), _loop(p, t, THR29))
+
+
 GOLD = [f for f in curve_fixtures() if "best" in f]
 
 
