@@ -5,18 +5,18 @@
 #include <stdint.h>
 
 #include "mpvae_hip.h"
+#include "workspace.h"
 
 namespace mpv {
 
 // Record a message for mpv_last_error() and return `code`.
 int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 
-// After a kernel launch: MPV_OK, or MPV_ELAUNCH with the HIP error text.
+// After a kernel launch: MPV_OK, or MPV_ELAUNCH with the HIP error text.  For
+// MPV_LAUNCH alone.
 int check_launch(const char* what);
 
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
@@ -51,11 +51,16 @@ class TimedLaunch {
 
 }  // namespace mpv
 
-// hipLaunchKernelGGL under a TimedLaunch scope named `tag`.
+// The one launch form: hipLaunchKernelGGL under a TimedLaunch scope named
+// `tag`, then, the scope closed, hipGetLastError(); a failed launch returns
+// MPV_ELAUNCH, its message naming `kernel`, from the enclosing function.
 #define MPV_LAUNCH(tag, kernel, grid, block, shm, stream, ...)                  \
   do {                                                                         \
-    ::mpv::TimedLaunch mpv_tl_(tag, stream);                                   \
-    hipLaunchKernelGGL(kernel, grid, block, shm, stream, __VA_ARGS__);         \
+    {                                                                          \
+      ::mpv::TimedLaunch mpv_tl_(tag, stream);                                 \
+      hipLaunchKernelGGL(kernel, grid, block, shm, stream, __VA_ARGS__);       \
+    }                                                                          \
+    if (int mpv_rc_ = ::mpv::check_launch(#kernel)) return mpv_rc_;            \
   } while (0)
 
 #define MPV_REQUIRE(cond, ...)                         \

@@ -28,7 +28,7 @@ constexpr int kCalThreads = 256;
 constexpr int kCalTile = 4;       // targets whose sums a thread holds in registers at once
 constexpr double kCalEps = 1e-6;  // the reference's 1e-6 (logit, the BCE logs)
 
-// Workspace, in doubles.
+// Workspace.
 struct CalibWs {
   double* bpart;   // (NLB, G, R)   BCE partials
   double* wpart;   // (T, G, R)     sum of w over the slice's rows
@@ -37,22 +37,21 @@ struct CalibWs {
   double* dtab;    // (T, G, L)     2 (m_tk - m_t) / W_tk
   double* etab;    // (T, L)        sum_k 2 (m_tk - m_t) / W_t
   double* dxpart;  // (G, R, L)     d threshold partials
-  size_t total;
 };
 
-static CalibWs calib_ws(void* ws, int64_t L, int64_t T, int64_t G, int64_t R) {
-  const int64_t nlb = cdiv(L, kCalThreads);
+static CalibWs calib_ws(Workspace& ws, int64_t L, int64_t T, int64_t G, int64_t R) {
   CalibWs c;
-  c.bpart = reinterpret_cast<double*>(ws);
-  c.wpart = c.bpart + nlb * G * R;
-  c.qpart = c.wpart + T * G * R;
-  c.wsum = c.qpart + T * G * R * L;
-  c.dtab = c.wsum + T * (G + 1);
-  c.etab = c.dtab + T * G * L;
-  c.dxpart = c.etab + T * L;
-  c.total = (size_t)(nlb * G * R + T * G * R * (1 + L) + T * (G + 1) + T * G * L + T * L + G * R * L);
+  c.bpart = ws.take<double>(cdiv(L, kCalThreads), G, R);
+  c.wpart = ws.take<double>(T, G, R);
+  c.qpart = ws.take<double>(T, G, R, L);
+  c.wsum = ws.take<double>(T, G + 1);
+  c.dtab = ws.take<double>(T, G, L);
+  c.etab = ws.take<double>(T, L);
+  c.dxpart = ws.take<double>(G, R, L);
   return c;
 }
+
+static bool calib_shape_ok(int64_t L, int64_t T, int64_t G) { return L >= 1 && T >= 0 && G >= 1; }
 
 // The threshold of (label l, group k) and what the calibration needs of it:
 // c = logit(thr) (:40), and for the backward d c / d threshold_.
@@ -242,14 +241,15 @@ using namespace mpv;
 extern "C" {
 
 size_t mpv_calib_workspace_bytes(int64_t L, int64_t T, int64_t G, int64_t R) {
-  if (L <= 0 || T < 0 || G <= 0 || R <= 0) return 0;
-  return sizeof(double) * calib_ws(nullptr, L, T, G, R).total;
+  if (!calib_shape_ok(L, T, G) || R < 1) return 0;
+  return layout_bytes(calib_ws, L, T, G, R);
 }
 
-static int calib_check(const mpv_calib_args* a, void* workspace, size_t workspace_bytes) {
+static int calib_check(const mpv_calib_args* a, void* workspace, size_t workspace_bytes,
+                       CalibWs* ws) {
   MPV_REQUIRE(a != nullptr, "mpv_calib_args is NULL");
   MPV_REQUIRE(a->p != nullptr, "NULL p in mpv_calib_args");
-  MPV_REQUIRE(a->B >= 1 && a->L >= 1 && a->G >= 1 && a->T >= 0,
+  MPV_REQUIRE(a->B >= 1 && calib_shape_ok(a->L, a->T, a->G),
               "bad calibration shape B=%lld L=%lld T=%lld G=%lld", (long long)a->B,
               (long long)a->L, (long long)a->T, (long long)a->G);
   MPV_REQUIRE(a->R >= 1, "calibration row slices R must be >= 1 (got %lld)", (long long)a->R);
@@ -258,38 +258,37 @@ static int calib_check(const mpv_calib_args* a, void* workspace, size_t workspac
               "calibration shape too large");
   MPV_REQUIRE(a->order && a->goff, "NULL order / goff in mpv_calib_args");
   MPV_REQUIRE(a->T == 0 || a->w != nullptr, "NULL w with T > 0");
-  MPV_REQUIRE(workspace && workspace_bytes >= mpv_calib_workspace_bytes(a->L, a->T, a->G, a->R),
-              "calibration workspace too small");
+  Workspace carve(workspace);
+  *ws = calib_ws(carve, a->L, a->T, a->G, a->R);
+  MPV_REQUIRE(carve.fits(workspace_bytes), "calibration workspace too small");
   return MPV_OK;
 }
 
 int mpv_calib_fwd(const mpv_calib_args* a, void* workspace, size_t workspace_bytes, void* stream) {
-  if (int rc = calib_check(a, workspace, workspace_bytes)) return rc;
+  CalibWs ws;
+  if (int rc = calib_check(a, workspace, workspace_bytes, &ws)) return rc;
   MPV_REQUIRE(a->out != nullptr, "NULL out in mpv_calib_args");
   hipStream_t st = as_stream(stream);
-  const CalibWs ws = calib_ws(workspace, a->L, a->T, a->G, a->R);
   const int nlb = (int)cdiv(a->L, kCalThreads);
   MPV_LAUNCH("calib_fwd", calib_fwd_kernel, dim3(nlb, (unsigned)a->G, (unsigned)a->R),
              dim3(kCalThreads), 0, st, *a, ws);
-  if (int rc = check_launch("calib_fwd")) return rc;
   MPV_LAUNCH("calib_tables", calib_tables_kernel, dim3(1), dim3(kCalThreads), 0, st, *a, ws, nlb);
-  return check_launch("calib_tables");
+  return MPV_OK;
 }
 
 int mpv_calib_bwd(const mpv_calib_args* a, const double* gout, float* g_threshold, float* g_p,
                   void* workspace, size_t workspace_bytes, void* stream) {
-  if (int rc = calib_check(a, workspace, workspace_bytes)) return rc;
+  CalibWs ws;
+  if (int rc = calib_check(a, workspace, workspace_bytes, &ws)) return rc;
   MPV_REQUIRE(a->threshold != nullptr, "mpv_calib_bwd needs a threshold");
   MPV_REQUIRE(gout && g_threshold, "NULL gout / g_threshold in mpv_calib_bwd");
   hipStream_t st = as_stream(stream);
-  const CalibWs ws = calib_ws(workspace, a->L, a->T, a->G, a->R);
   const int nlb = (int)cdiv(a->L, kCalThreads);
   MPV_LAUNCH("calib_bwd", calib_bwd_kernel, dim3(nlb, (unsigned)a->G, (unsigned)a->R),
              dim3(kCalThreads), 0, st, *a, ws, gout, g_p);
-  if (int rc = check_launch("calib_bwd")) return rc;
   MPV_LAUNCH("calib_bwd", calib_dx_kernel, dim3((unsigned)cdiv(a->L * a->G, 256)), dim3(256), 0, st,
              ws, (int)a->L, (int)a->G, (int)a->R, g_threshold);
-  return check_launch("calib_dx");
+  return MPV_OK;
 }
 
 }  // extern "C"

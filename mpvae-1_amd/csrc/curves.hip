@@ -332,6 +332,20 @@ static bool curve_chunk_ok(int64_t c) {
   return c == 0 || (c >= 64 && c <= kCurveChunk && (c & (c - 1)) == 0);
 }
 
+static bool curve_shape_ok(int64_t N, int64_t L) { return N > 0 && L > 0 && N <= INT32_MAX; }
+
+struct CurveWs {
+  uint64_t* cur;  // (L, N) keys
+  uint64_t* alt;  // the merge passes' second buffer, when chunks are merged
+};
+
+static CurveWs curve_ws(Workspace& ws, int64_t N, int64_t L, int64_t chunk) {
+  CurveWs c;
+  c.cur = ws.take<uint64_t>(N, L);
+  c.alt = ws.take<uint64_t>(N > (chunk ? chunk : kCurveChunk) ? N : 0, L);
+  return c;
+}
+
 }  // namespace mpv
 
 using namespace mpv;
@@ -339,54 +353,48 @@ using namespace mpv;
 extern "C" {
 
 size_t mpv_curves_workspace_bytes(int64_t N, int64_t L, int64_t chunk) {
-  if (N <= 0 || L <= 0 || N > INT32_MAX || !curve_chunk_ok(chunk)) return 0;
-  const size_t one = align_up(sizeof(uint64_t) * (size_t)N * (size_t)L, 256);
-  return N > (chunk ? chunk : kCurveChunk) ? 2 * one : one;  // + the merge passes' second buffer
+  if (!curve_shape_ok(N, L) || !curve_chunk_ok(chunk)) return 0;
+  return layout_bytes(curve_ws, N, L, chunk);
 }
 
 int mpv_curve_metrics(const mpv_curve_args* a, void* workspace, size_t workspace_bytes,
                       void* stream) {
   MPV_REQUIRE(a && a->pred && a->target && a->auc && a->aupr && a->fdr && a->agg,
               "NULL pointer in mpv_curve_args");
-  MPV_REQUIRE(a->N > 0 && a->L > 0 && a->N <= INT32_MAX, "bad curve shape N=%lld L=%lld",
-              (long long)a->N, (long long)a->L);
+  MPV_REQUIRE(curve_shape_ok(a->N, a->L), "bad curve shape N=%lld L=%lld", (long long)a->N,
+              (long long)a->L);
   MPV_REQUIRE(a->L <= kCurveMaxL, "label_dim %lld > %d is not supported by the curve aggregate",
               (long long)a->L, kCurveMaxL);
   MPV_REQUIRE(curve_chunk_ok(a->chunk),
               "chunk %lld must be 0 or a power of two in [64, %d]", (long long)a->chunk,
               kCurveChunk);
-  MPV_REQUIRE(workspace && workspace_bytes >= mpv_curves_workspace_bytes(a->N, a->L, a->chunk),
-              "curve workspace too small");
+  Workspace carve(workspace);
+  const CurveWs ws = curve_ws(carve, a->N, a->L, a->chunk);
+  MPV_REQUIRE(carve.fits(workspace_bytes), "curve workspace too small");
   hipStream_t st = as_stream(stream);
   const int64_t N = a->N;
   const int L = (int)a->L, chunk = a->chunk ? (int)a->chunk : kCurveChunk;
-  uint64_t* cur = reinterpret_cast<uint64_t*>(workspace);
-  uint64_t* alt = reinterpret_cast<uint64_t*>(
-      (char*)workspace + align_up(sizeof(uint64_t) * (size_t)N * (size_t)L, 256));
+  uint64_t *cur = ws.cur, *alt = ws.alt;
   MPV_LAUNCH("curve_keys", curve_keys_kernel,
              dim3((unsigned)cdiv(N, kKeyTile), (unsigned)cdiv(L, kKeyTile)), dim3(256), 0, st,
              a->pred, a->target, N, L, cur);
-  if (int rc = check_launch("curve_keys")) return rc;
   MPV_LAUNCH("curve_sort", curve_sort_kernel, dim3((unsigned)cdiv(N, chunk), (unsigned)L),
              dim3(kSortThreads), 0, st, cur, N, chunk);
-  if (int rc = check_launch("curve_sort")) return rc;
   for (int64_t w = chunk; w < N; w *= 2) {
     const int64_t pair = 2 * w < N ? 2 * w : N;
     const int tpp = (int)cdiv(pair, kMergeTile);
     MPV_LAUNCH("curve_merge", curve_merge_kernel,
                dim3((unsigned)(cdiv(N, 2 * w) * tpp), (unsigned)L), dim3(kMergeThreads), 0, st,
                cur, alt, N, w, tpp);
-    if (int rc = check_launch("curve_merge")) return rc;
     uint64_t* t = cur;
     cur = alt;
     alt = t;
   }
   MPV_LAUNCH("curve_pass", curve_pass_kernel, dim3((unsigned)L), dim3(kCurveThreads), 0, st, cur, N,
              a->auc, a->aupr, a->fdr);
-  if (int rc = check_launch("curve_pass")) return rc;
   MPV_LAUNCH("curve_agg", curve_agg_kernel, dim3(3), dim3(kSortThreads), 0, st, a->auc, a->aupr,
              a->fdr, L, a->agg);
-  return check_launch("curve_agg");
+  return MPV_OK;
 }
 
 }  // extern "C"

@@ -42,7 +42,7 @@ constexpr int kEvalTile = 4;                 // targets whose sums a lane holds 
 constexpr int kEvalVals = 3 + 2 * kEvalTile;  // tp, fp, fn, then (sum w p, sum w) per target
 constexpr double kEvalEps = 1e-6;            // evals.py:109
 
-// Workspace, in doubles.
+// Workspace.
 struct EvalWs {
   double* cpart;  // (G, R, 3, L)  tp / fp / fn partials
   double* wpart;  // (T, G, R)     sum of w over the slice's rows
@@ -51,22 +51,26 @@ struct EvalWs {
   double* gsum;   // (T, G, L)     sum_r qpart
   double* csum;   // (G, 3, L)     sum_r cpart
   double* mtab;   // (T, L)        m_t
-  size_t total;
 };
 
-static EvalWs eval_ws(void* ws, int64_t L, int64_t T, int64_t G, int64_t R) {
+static EvalWs eval_ws(Workspace& ws, int64_t L, int64_t T, int64_t G, int64_t R) {
   EvalWs c;
-  c.cpart = reinterpret_cast<double*>(ws);
-  c.wpart = c.cpart + G * R * 3 * L;
-  c.qpart = c.wpart + T * G * R;
-  c.wsum = c.qpart + T * G * R * L;
-  c.gsum = c.wsum + T * (G + 1);
-  c.csum = c.gsum + T * G * L;
-  c.mtab = c.csum + G * 3 * L;
-  c.total = (size_t)(G * R * 3 * L + T * G * R * (1 + L) + T * (G + 1) + T * G * L + G * 3 * L +
-                     T * L);
+  c.cpart = ws.take<double>(G, R, 3, L);
+  c.wpart = ws.take<double>(T, G, R);
+  c.qpart = ws.take<double>(T, G, R, L);
+  c.wsum = ws.take<double>(T, G + 1);
+  c.gsum = ws.take<double>(T, G, L);
+  c.csum = ws.take<double>(G, 3, L);
+  c.mtab = ws.take<double>(T, L);
   return c;
 }
+
+// T targets in each of D >= 1 definitions, at most 2^20 in all.
+static bool split_shape_ok(int64_t N, int64_t L, int64_t T, int64_t D, int64_t G) {
+  return N > 0 && N < (int64_t(1) << 31) && L > 0 && L <= 4096 && T >= 0 &&
+         T <= (int64_t(1) << 20) / D && G >= 1 && G <= 65535;
+}
+static bool split_slices_ok(int64_t R) { return R >= 1 && R <= 65535; }
 
 // Lanes along the labels: the power of two >= L up to 32, else 64.
 static int eval_lanes(int64_t L) {
@@ -275,11 +279,10 @@ static int split_eval_run(const mpv_split_eval_args* a, int64_t D, double* out_d
   MPV_REQUIRE(a != nullptr, "mpv_split_eval_args is NULL");
   MPV_REQUIRE(D >= 1 && D <= (int64_t(1) << 20), "definitions D must be in 1 .. 2^20 (got %lld)",
               (long long)D);
-  MPV_REQUIRE(a->N > 0 && a->N < (int64_t(1) << 31) && a->L > 0 && a->L <= 4096 && a->T >= 0 &&
-                  a->T * D <= (int64_t(1) << 20) && a->G >= 1 && a->G <= 65535,
+  MPV_REQUIRE(split_shape_ok(a->N, a->L, a->T, D, a->G),
               "bad split shape N=%lld L=%lld T=%lld G=%lld", (long long)a->N, (long long)a->L,
               (long long)(a->T * D), (long long)a->G);
-  MPV_REQUIRE(a->R >= 1 && a->R <= 65535, "split row slices R must be in 1 .. 65535 (got %lld)",
+  MPV_REQUIRE(split_slices_ok(a->R), "split row slices R must be in 1 .. 65535 (got %lld)",
               (long long)a->R);
   MPV_REQUIRE(a->pred && a->target, "NULL pred / target in mpv_split_eval_args");
   MPV_REQUIRE(a->goff != nullptr || a->G == 1, "NULL goff with G = %lld groups", (long long)a->G);
@@ -287,28 +290,24 @@ static int split_eval_run(const mpv_split_eval_args* a, int64_t D, double* out_d
   MPV_REQUIRE(a->counts && a->out, "NULL counts / out in mpv_split_eval_args");
   mpv_split_eval_args all = *a;
   all.T = a->T * D;
-  const size_t need = mpv_split_eval_workspace_bytes(all.N, all.L, all.T, all.G, all.R);
-  MPV_REQUIRE(workspace && need && workspace_bytes >= need, "split workspace too small");
+  Workspace carve(workspace);
+  const EvalWs ws = eval_ws(carve, all.L, all.T, all.G, all.R);
+  MPV_REQUIRE(carve.fits(workspace_bytes), "split workspace too small");
   hipStream_t st = as_stream(stream);
-  const EvalWs ws = eval_ws(workspace, all.L, all.T, all.G, all.R);
   const int lp = eval_lanes(all.L);
   MPV_LAUNCH("split_eval", split_eval_kernel,
              dim3((unsigned)cdiv(all.L, lp), (unsigned)all.G, (unsigned)all.R), dim3(kEvalThreads),
              0, st, all, ws, lp);
-  if (int rc = check_launch("split_eval")) return rc;
   MPV_LAUNCH("split_final", split_final_kernel, dim3(1), dim3(kEvalThreads), 0, st, all, ws,
              (int)D, out_defs);
-  return check_launch("split_final");
+  return MPV_OK;
 }
 
 extern "C" {
 
 size_t mpv_split_eval_workspace_bytes(int64_t N, int64_t L, int64_t T, int64_t G, int64_t R) {
-  if (N <= 0 || N >= (int64_t(1) << 31) || L <= 0 || L > 4096 || T < 0 || G < 1 || G > 65535 ||
-      R < 1 || R > 65535 || T > (int64_t(1) << 20))
-    return 0;
-  if ((double)G * (double)R * (double)(L + 1) * (double)(T + 3) > 1e12) return 0;  // no overflow below
-  return sizeof(double) * eval_ws(nullptr, L, T, G, R).total;
+  if (!split_shape_ok(N, L, T, 1, G) || !split_slices_ok(R)) return 0;
+  return layout_bytes(eval_ws, L, T, G, R);
 }
 
 int mpv_split_eval(const mpv_split_eval_args* a, void* workspace, size_t workspace_bytes,

@@ -489,11 +489,11 @@ static int check_label_table(const mpv_label_table* tab, int64_t L) {
 
 // T sources in launches of a Set's capacity each, chunk t0 filling rows t0 ..
 // of w (the unused slots of the last chunk repeat its first source).  `tag` is
-// the timing label, `what` names the launch in an error.
+// the timing label.
 template <typename Set, typename Src>
-static int launch_row_weights(const char* tag, const char* what, const float* y, int64_t B,
-                              int64_t L, const Src* src, int64_t T, double* w,
-                              int32_t* contributed, void* stream) {
+static int launch_row_weights(const char* tag, const float* y, int64_t B, int64_t L,
+                              const Src* src, int64_t T, double* w, int32_t* contributed,
+                              void* stream) {
   constexpr int64_t cap = sizeof(Set::s) / sizeof(Src);
   const int blocks = (int)cdiv(B, kLwWaves);
   for (int64_t t0 = 0; t0 < T; t0 += cap) {
@@ -502,19 +502,51 @@ static int launch_row_weights(const char* tag, const char* what, const float* y,
     for (int64_t i = 0; i < cap; ++i) set.s[i] = src[t0 + (i < set.n ? i : 0)];
     MPV_LAUNCH(tag, row_weights_kernel<Set>, dim3(blocks), dim3(64 * kLwWaves), 0,
                as_stream(stream), y, (int)B, (int)L, set, w + t0 * B, contributed);
-    if (int rc = check_launch(what)) return rc;
   }
   return MPV_OK;
 }
 
 template <typename T>
-static void launch_group_rows(const void* x, int B, int n, int G, int32_t* gid, int32_t* order,
+static int launch_group_rows(const void* x, int B, int n, int G, int32_t* gid, int32_t* order,
                               int32_t* goff, uint8_t* overflow, hipStream_t st) {
   const size_t bytes = sizeof(T) * (size_t)B * n;
   const int stage = bytes <= (size_t)kGroupStageBytes;
-  const int threads = B >= kGroupThreads ? kGroupThreads : (int)align_up(B, 64);
+  const int threads = B >= kGroupThreads ? kGroupThreads : (int)cdiv(B, 64) * 64;
   MPV_LAUNCH("group_rows", group_rows_kernel<T>, dim3(1), dim3(threads), stage ? bytes : 0, st,
              static_cast<const T*>(x), B, n, G, stage, gid, order, goff, overflow);
+  return MPV_OK;
+}
+
+static bool fair_shape_ok(int64_t L, int64_t T, int64_t G) { return L > 0 && T > 0 && G > 0; }
+
+struct FairWs {
+  double* dtab;  // (2, T, G, L)
+  double* etab;  // (2, T, L)
+  double* wsum;  // (T, G + 1)
+  double* part;  // (2 NLB)  penalty partials
+};
+
+static FairWs fair_ws(Workspace& ws, int64_t L, int64_t T, int64_t G) {
+  FairWs f;
+  f.dtab = ws.take<double>(2, T, G, L);
+  f.etab = ws.take<double>(2, T, L);
+  f.wsum = ws.take<double>(T, G + 1);
+  f.part = ws.take<double>(2, cdiv(L, kFairThreads));
+  return f;
+}
+
+static bool metrics_shape_ok(int64_t B, int64_t L) { return B > 0 && L > 0; }
+
+struct MetricsWs {
+  double* rowstat;  // (B, 8)
+  float* colstat;   // (3, L)
+};
+
+static MetricsWs metrics_ws(Workspace& ws, int64_t B, int64_t L) {
+  MetricsWs m;
+  m.rowstat = ws.take<double>(B, 8);
+  m.colstat = ws.take<float>(3, L);
+  return m;
 }
 
 extern "C" {
@@ -523,8 +555,8 @@ int mpv_label_weights(const float* y, int64_t B, int64_t L, const mpv_label_tabl
                       double* w, int32_t* contributed, void* stream) {
   MPV_REQUIRE(y && tab && w && contributed && B > 0 && L > 0, "bad label_weights arguments");
   if (int rc = check_label_table(tab, L)) return rc;
-  return launch_row_weights<LabelTables<1>>("label_weights", "label_weights", y, B, L, tab, 1, w,
-                                            contributed, stream);
+  return launch_row_weights<LabelTables<1>>("label_weights", y, B, L, tab, 1, w, contributed,
+                                            stream);
 }
 
 int mpv_label_weights_batch(const float* y, int64_t B, int64_t L, const mpv_label_table* tables,
@@ -534,7 +566,7 @@ int mpv_label_weights_batch(const float* y, int64_t B, int64_t L, const mpv_labe
   for (int64_t t = 0; t < T; ++t)  // every table is checked before the first launch
     if (int rc = check_label_table(tables + t, L)) return rc;
   return launch_row_weights<LabelTables<MPV_LABEL_TABLES_PER_LAUNCH>>(
-      "label_weights", "label_weights_batch", y, B, L, tables, T, w, contributed, stream);
+      "label_weights", y, B, L, tables, T, w, contributed, stream);
 }
 
 int mpv_label_sim_weights(const float* y, int64_t B, int64_t L, const mpv_label_sim* sims,
@@ -547,8 +579,7 @@ int mpv_label_sim_weights(const float* y, int64_t B, int64_t L, const mpv_label_
     MPV_REQUIRE(sims[t].kind >= MPV_SIM_INDICATION && sims[t].kind <= MPV_SIM_HAMMING,
                 "similarity %lld: unknown kind %d", (long long)t, (int)sims[t].kind);
   }
-  return launch_row_weights<LabelSims>("label_sim", "label_sim", y, B, L, sims, T, w, contributed,
-                                       stream);
+  return launch_row_weights<LabelSims>("label_sim", y, B, L, sims, T, w, contributed, stream);
 }
 
 int mpv_group_rows(const void* x, int x_elem, int64_t B, int64_t n, int64_t G, int32_t* gid,
@@ -562,95 +593,75 @@ int mpv_group_rows(const void* x, int x_elem, int64_t B, int64_t n, int64_t G, i
   hipStream_t st = as_stream(stream);
   switch (x_elem) {
     case MPV_EL_F32:
-      launch_group_rows<float>(x, (int)B, (int)n, (int)G, gid, order, goff, overflow, st);
-      break;
+      return launch_group_rows<float>(x, (int)B, (int)n, (int)G, gid, order, goff, overflow, st);
     case MPV_EL_F64:
-      launch_group_rows<double>(x, (int)B, (int)n, (int)G, gid, order, goff, overflow, st);
-      break;
+      return launch_group_rows<double>(x, (int)B, (int)n, (int)G, gid, order, goff, overflow, st);
     case MPV_EL_I32:
-      launch_group_rows<int32_t>(x, (int)B, (int)n, (int)G, gid, order, goff, overflow, st);
-      break;
+      return launch_group_rows<int32_t>(x, (int)B, (int)n, (int)G, gid, order, goff, overflow, st);
     case MPV_EL_I64:
-      launch_group_rows<int64_t>(x, (int)B, (int)n, (int)G, gid, order, goff, overflow, st);
-      break;
+      return launch_group_rows<int64_t>(x, (int)B, (int)n, (int)G, gid, order, goff, overflow, st);
     default:
       return fail(MPV_EINVAL, "mpv_group_rows: unknown element type %d", x_elem);
   }
-  return check_launch("group_rows");
 }
 
 size_t mpv_fair_workspace_bytes(int64_t L, int64_t T, int64_t G) {
-  if (L <= 0 || T <= 0 || G <= 0) return 0;
-  const int64_t nlb = cdiv(L, kFairThreads);
-  return sizeof(double) * (size_t)(2 * T * G * L + 2 * T * L + T * (G + 1) + 2 * nlb);
-}
-
-static void fair_ws(const mpv_fair_args* a, void* ws, double*& dtab, double*& etab, double*& wsum,
-                    double*& part) {
-  dtab = reinterpret_cast<double*>(ws);
-  etab = dtab + 2 * a->T * a->G * a->L;
-  wsum = etab + 2 * a->T * a->L;
-  part = wsum + a->T * (a->G + 1);
+  if (!fair_shape_ok(L, T, G)) return 0;
+  return layout_bytes(fair_ws, L, T, G);
 }
 
 int mpv_fair_fwd(const mpv_fair_args* a, void* workspace, size_t workspace_bytes, void* stream) {
   MPV_REQUIRE(a && a->label_z && a->feat_z && a->w && a->order && a->goff && a->gid && a->out,
               "NULL pointer in mpv_fair_args");
-  MPV_REQUIRE(a->B > 0 && a->L > 0 && a->T > 0 && a->G > 0, "bad fairness shape");
-  MPV_REQUIRE(workspace && workspace_bytes >= mpv_fair_workspace_bytes(a->L, a->T, a->G),
-              "fairness workspace too small");
+  MPV_REQUIRE(a->B > 0 && fair_shape_ok(a->L, a->T, a->G), "bad fairness shape");
+  Workspace carve(workspace);
+  const FairWs ws = fair_ws(carve, a->L, a->T, a->G);
+  MPV_REQUIRE(carve.fits(workspace_bytes), "fairness workspace too small");
   hipStream_t st = as_stream(stream);
-  double *dtab, *etab, *wsum, *part;
-  fair_ws(a, workspace, dtab, etab, wsum, part);
   const int npair = (int)(a->T * (a->G + 1));
   MPV_LAUNCH("fair_fwd", fair_wsum_kernel, dim3((unsigned)cdiv(npair, 64)), dim3(64), 0, st, a->w,
-             a->order, a->goff, (int)a->B, (int)a->T, (int)a->G, wsum);
-  if (int rc = check_launch("fair_wsum")) return rc;
+             a->order, a->goff, (int)a->B, (int)a->T, (int)a->G, ws.wsum);
   const int nlb = (int)cdiv(a->L, kFairThreads);
-  MPV_LAUNCH("fair_fwd", fair_fwd_kernel, dim3(nlb, 2), dim3(kFairThreads), 0, st, *a, wsum, dtab,
-             etab, part);
-  if (int rc = check_launch("fair_fwd")) return rc;
-  MPV_LAUNCH("fair_fwd", fair_final_kernel, dim3(1), dim3(64), 0, st, part, 2 * nlb, a->fair_coeff,
-             a->out);
-  return check_launch("fair_final");
+  MPV_LAUNCH("fair_fwd", fair_fwd_kernel, dim3(nlb, 2), dim3(kFairThreads), 0, st, *a, ws.wsum,
+             ws.dtab, ws.etab, ws.part);
+  MPV_LAUNCH("fair_fwd", fair_final_kernel, dim3(1), dim3(64), 0, st, ws.part, 2 * nlb,
+             a->fair_coeff, a->out);
+  return MPV_OK;
 }
 
 int mpv_fair_bwd(const mpv_fair_args* a, const double* gout, float* g_label_z, float* g_feat_z,
                  void* workspace, size_t workspace_bytes, void* stream) {
   MPV_REQUIRE(a && gout && g_label_z && g_feat_z && a->w && a->gid, "NULL pointer in fair_bwd");
-  MPV_REQUIRE(workspace && workspace_bytes >= mpv_fair_workspace_bytes(a->L, a->T, a->G),
-              "fairness workspace too small");
-  double *dtab, *etab, *wsum, *part;
-  fair_ws(a, workspace, dtab, etab, wsum, part);
+  Workspace carve(workspace);
+  const FairWs ws = fair_ws(carve, a->L, a->T, a->G);
+  MPV_REQUIRE(carve.fits(workspace_bytes), "fairness workspace too small");
   const int64_t n = a->B * a->L;
   MPV_LAUNCH("fair_bwd", fair_bwd_kernel, dim3((unsigned)cdiv(n, kFairThreads), 2),
-             dim3(kFairThreads), 0, as_stream(stream), *a, dtab, etab, gout, g_label_z, g_feat_z);
-  return check_launch("fair_bwd");
+             dim3(kFairThreads), 0, as_stream(stream), *a, ws.dtab, ws.etab, gout, g_label_z,
+             g_feat_z);
+  return MPV_OK;
 }
 
 size_t mpv_metrics_workspace_bytes(int64_t B, int64_t L) {
-  if (B <= 0 || L <= 0) return 0;
-  return align_up(sizeof(double) * 8 * (size_t)B, 256) + sizeof(float) * 3 * (size_t)L;
+  if (!metrics_shape_ok(B, L)) return 0;
+  return layout_bytes(metrics_ws, B, L);
 }
 
 int mpv_train_metrics(const float* pred, const float* target, int64_t B, int64_t L,
                       float threshold, double* out, void* workspace, size_t workspace_bytes,
                       void* stream) {
-  MPV_REQUIRE(pred && target && out && B > 0 && L > 0, "bad train_metrics arguments");
-  MPV_REQUIRE(workspace && workspace_bytes >= mpv_metrics_workspace_bytes(B, L),
-              "metrics workspace too small");
+  MPV_REQUIRE(pred && target && out && metrics_shape_ok(B, L), "bad train_metrics arguments");
+  Workspace carve(workspace);
+  const MetricsWs ws = metrics_ws(carve, B, L);
+  MPV_REQUIRE(carve.fits(workspace_bytes), "metrics workspace too small");
   hipStream_t st = as_stream(stream);
-  double* rowstat = reinterpret_cast<double*>(workspace);
-  float* colstat = reinterpret_cast<float*>((char*)workspace + align_up(sizeof(double) * 8 * B, 256));
   MPV_LAUNCH("metrics", metric_rows_kernel, dim3((unsigned)B), dim3(kMetThreads), 0, st, pred,
-             target, (int)B, (int)L, threshold, rowstat);
-  if (int rc = check_launch("metric_rows")) return rc;
+             target, (int)B, (int)L, threshold, ws.rowstat);
   MPV_LAUNCH("metrics", metric_cols_kernel, dim3((unsigned)cdiv(L, 256)), dim3(256), 0, st, pred,
-             target, (int)B, (int)L, threshold, colstat);
-  if (int rc = check_launch("metric_cols")) return rc;
-  MPV_LAUNCH("metrics", metric_final_kernel, dim3(1), dim3(64), 0, st, rowstat, colstat, (int)B,
-             (int)L, out);
-  return check_launch("metric_final");
+             target, (int)B, (int)L, threshold, ws.colstat);
+  MPV_LAUNCH("metrics", metric_final_kernel, dim3(1), dim3(64), 0, st, ws.rowstat, ws.colstat,
+             (int)B, (int)L, out);
+  return MPV_OK;
 }
 
 }  // extern "C"

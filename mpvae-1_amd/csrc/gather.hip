@@ -186,10 +186,7 @@ extern "C" int mpv_gather_batch(const mpv_gather_args* args, void* stream) {
   hipStream_t s = as_stream(stream);
   MPV_LAUNCH("gather_batch", gather_batch_kernel, dim3((unsigned)cdiv(a.B, kGatherRows)),
              dim3(kGatherThreads), 0, s, a);
-  if (int rc = check_launch("gather_batch")) return rc;
-  if (args->advance) {
+  if (args->advance)
     MPV_LAUNCH("gather_batch", gather_advance_kernel, dim3(1), dim3(64), 0, s, args->pos, a.B);
-    return check_launch("gather_batch");
-  }
   return MPV_OK;
 }

@@ -37,29 +37,11 @@ constexpr int kLinThreads = 256;  // 4 waves
 constexpr int kLinWant = 512;     // workgroups per launch to aim for (2 per CU)
 constexpr int kLinMinChunk = 32;  // reduction rows per split, at least
 
-struct LinParams {
-  int64_t M, N, R;
-  const float* a;
-  int64_t a_si, a_sr;
-  const float* a_mask;
-  float a_scale;
-  const float* b;
-  int64_t b_sj, b_sr;
-  int64_t ones_col;  // j == ones_col reads B = 1 (bias-gradient column), -1: none
-  const float* bias;
-  float alpha;
-  int relu;
-  float* out;
-  int64_t out_si;
-  float* out_col;
+// A problem as the kernels see it: mpv_linear_args with ones_col < 0 as -1 and
+// R1 = R without a second segment, and where its split-K partials go.
+struct LinParams : mpv_linear_args {
   float* part;    // (nsplit, M, N) chunk partials, null: direct epilogue
   int64_t chunk;  // reduction rows per split
-  // second reduction segment (a2 != null): reduction index r >= R1 reads
-  // A = a2 (row stride a2_si) and B = b2 (B's strides) at r - R1
-  const float* a2;
-  int64_t a2_si;
-  const float* b2;
-  int64_t R1;
 };
 
 // kLinPer elements of a 64-row x 64-reduction operand tile, mapped so that
@@ -223,7 +205,6 @@ __global__ __launch_bounds__(256) void lin_reduce_kernel(LinBatch bt) {
 
 struct LinPlan {
   int64_t ti, tj, nsplit, chunk;
-  size_t part_bytes;
 };
 
 LinPlan plan_linear(int64_t M, int64_t N, int64_t R) {
@@ -234,8 +215,32 @@ LinPlan plan_linear(int64_t M, int64_t N, int64_t R) {
   want = std::max<int64_t>(1, std::min<int64_t>(want, cdiv(R, kLinMinChunk)));
   pl.chunk = std::max<int64_t>(kLinStep, cdiv(cdiv(R, want), kLinStep) * kLinStep);
   pl.nsplit = std::max<int64_t>(1, cdiv(R, pl.chunk));
-  pl.part_bytes = pl.nsplit > 1 ? align_up(sizeof(float) * pl.nsplit * M * N, 256) : 0;
   return pl;
+}
+
+bool linear_count_ok(const mpv_linear_args* args, int n) {
+  return args != nullptr && n >= 1 && n <= kLinMaxProb;
+}
+
+// The workspace of a batch: each problem's split-K partials, in order (none
+// for one chunk, nor for a problem without output or with bad sizes, which
+// mpv_linear_batch skips or reports).  end[k]: the bytes problems 0 .. k need.
+struct LinWs {
+  float* part[kLinMaxProb];
+  size_t end[kLinMaxProb];
+};
+
+LinWs linear_ws(Workspace& ws, const mpv_linear_args* args, int n) {
+  LinWs w{};
+  for (int k = 0; k < n; ++k) {
+    const mpv_linear_args& a = args[k];
+    if (a.M > 0 && a.N > 0 && a.R >= 0) {
+      const int64_t nsplit = plan_linear(a.M, a.N, a.R).nsplit;
+      w.part[k] = ws.take<float>(nsplit > 1 ? nsplit : 0, a.M, a.N);
+    }
+    w.end[k] = ws.bytes();
+  }
+  return w;
 }
 
 }  // namespace
@@ -245,29 +250,29 @@ using namespace mpv;
 
 extern "C" {
 
-size_t mpv_linear_workspace_bytes(int64_t M, int64_t N, int64_t R) {
-  if (M <= 0 || N <= 0 || R < 0) return 0;
-  return plan_linear(M, N, R).part_bytes;
+size_t mpv_linear_batch_workspace_bytes(const mpv_linear_args* args, int n) {
+  if (!linear_count_ok(args, n)) return 0;
+  return layout_bytes(linear_ws, args, n);
 }
 
-size_t mpv_linear_batch_workspace_bytes(const mpv_linear_args* args, int n) {
-  size_t total = 0;
-  for (int q = 0; args != nullptr && q < n; ++q)
-    total += mpv_linear_workspace_bytes(args[q].M, args[q].N, args[q].R);
-  return total;
+size_t mpv_linear_workspace_bytes(int64_t M, int64_t N, int64_t R) {
+  mpv_linear_args a{};
+  a.M = M;
+  a.N = N;
+  a.R = R;
+  return mpv_linear_batch_workspace_bytes(&a, 1);
 }
 
 int mpv_linear_batch(const mpv_linear_args* args, int n, void* workspace, size_t workspace_bytes,
                      void* stream) {
-  MPV_REQUIRE(args != nullptr && n >= 1 && n <= kLinMaxProb, "linear: 1..%d problems per launch",
-              kLinMaxProb);
+  MPV_REQUIRE(linear_count_ok(args, n), "linear: 1..%d problems per launch", kLinMaxProb);
+  Workspace carve(workspace);
+  const LinWs ws = linear_ws(carve, args, n);
   LinBatch bt;
   bt.n = 0;
   bt.zoff[0] = 0;
   bt.eoff[0] = 0;
   int64_t gx = 0, gy = 0;
-  size_t off = 0;
-  char* ws = reinterpret_cast<char*>(workspace);
   for (int k = 0; k < n; ++k) {
     const mpv_linear_args* a = &args[k];
     MPV_REQUIRE(a->M >= 0 && a->N >= 0 && a->R >= 0, "bad linear sizes (problem %d)", k);
@@ -280,37 +285,19 @@ int mpv_linear_batch(const mpv_linear_args* args, int n, void* workspace, size_t
                 "linear: output too large for the grid");
     const LinPlan pl = plan_linear(a->M, a->N, a->R);
     MPV_REQUIRE(bt.zoff[bt.n] + pl.nsplit < 65535, "linear: too many reduction chunks");
-    MPV_REQUIRE(off + pl.part_bytes <= workspace_bytes && (pl.part_bytes == 0 || workspace != nullptr),
-                "linear: workspace %zu < %zu bytes", workspace_bytes, off + pl.part_bytes);
-    LinParams& p = bt.p[bt.n];
-    p.M = a->M;
-    p.N = a->N;
-    p.R = a->R;
-    p.a = a->a;
-    p.a_si = a->a_si;
-    p.a_sr = a->a_sr;
-    p.a_mask = a->a_mask;
-    p.a_scale = a->a_scale;
-    p.b = a->b;
-    p.b_sj = a->b_sj;
-    p.b_sr = a->b_sr;
-    p.ones_col = a->ones_col < 0 ? -1 : a->ones_col;
-    p.bias = a->bias;
-    p.alpha = a->alpha;
-    p.relu = a->relu;
-    p.out = a->out;
-    p.out_si = a->out_si;
-    p.out_col = a->out_col;
+    // (the problems up to k passed the two checks above, so none of their
+    // pieces was refused and end[k] is their sum)
+    MPV_REQUIRE(ws.end[k] <= workspace_bytes && (pl.nsplit == 1 || ws.part[k] != nullptr),
+                "linear: workspace %zu < %zu bytes", workspace_bytes, ws.end[k]);
     MPV_REQUIRE((a->a2 == nullptr) == (a->b2 == nullptr) &&
                     (a->a2 == nullptr || (a->a_mask == nullptr && a->R1 >= 0 && a->R1 <= a->R)),
                 "linear: a second segment needs a2 and b2, no mask, 0 <= R1 <= R (problem %d)", k);
-    p.a2 = a->a2;
-    p.a2_si = a->a2_si;
-    p.b2 = a->b2;
+    LinParams& p = bt.p[bt.n];
+    static_cast<mpv_linear_args&>(p) = *a;
+    p.ones_col = a->ones_col < 0 ? -1 : a->ones_col;
     p.R1 = a->a2 != nullptr ? a->R1 : a->R;
-    p.part = pl.nsplit > 1 ? reinterpret_cast<float*>(ws + off) : nullptr;
+    p.part = ws.part[k];
     p.chunk = pl.chunk;
-    off += pl.part_bytes;
     bt.ti[bt.n] = (int)pl.ti;
     bt.tj[bt.n] = (int)pl.tj;
     bt.zoff[bt.n + 1] = bt.zoff[bt.n] + (int)pl.nsplit;
@@ -332,7 +319,7 @@ int mpv_linear_batch(const mpv_linear_args* args, int n, void* workspace, size_t
   if (bt.eoff[bt.n] > 0)
     MPV_LAUNCH("linear", lin_reduce_kernel,
                dim3((unsigned)std::min<int64_t>(cdiv(bt.eoff[bt.n], 256), 2048)), dim3(256), 0, st, bt);
-  return check_launch("linear");
+  return MPV_OK;
 }
 
 int mpv_linear(const mpv_linear_args* a, void* workspace, size_t workspace_bytes, void* stream) {

@@ -27,13 +27,12 @@ constexpr float kKlWeight = 1.1f;
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // An MPV_F32 / MPV_F64 tag as a type: calls f(float{}) or f(double{}), so a
-// generic lambda reads the element type off its argument (host and device).
+// generic lambda reads the element type off its argument (host and device);
+// returns what f returns.
 template <typename F>
-__host__ __device__ __forceinline__ void with_dtype(int dtype, F&& f) {
-  if (dtype == MPV_F64)
-    f(double{});
-  else
-    f(float{});
+__host__ __device__ __forceinline__ auto with_dtype(int dtype, F&& f) {
+  if (dtype == MPV_F64) return f(double{});
+  return f(float{});
 }
 
 // Hardware transcendentals (v_exp_f32 / v_log_f32 are base 2).

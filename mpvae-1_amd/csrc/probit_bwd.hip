@@ -1299,12 +1299,12 @@ struct BwdPlan {
   int TPR, RPI, nLc, nSc, rows_per_chunk, Lc;   // element pass
   int nLt, nZt, nKc, dr_rows_per_chunk, rows_pad;  // dR GEMM
   int64_t ldg;                                  // G plane columns (3xf16, padded)
-  // the workspace: coef | colpart | slab | bound | G planes, each 256-B aligned
-  size_t coef_off, colpart_off, slab_off, bound_off, planes_off, end_off;
-  size_t total_bytes() const { return end_off; }
+  // the workspace's pieces (NULL from the sizing pass)
+  float *coef, *colpart, *slab, *gbound;
+  uint16_t* g16;  // G planes, chunked: rows_pad rows of 2 * ldg halves; 3xf16 only
 };
 
-static BwdPlan plan_bwd(const mpv_shape* s, int gemm) {
+static BwdPlan plan_bwd(Workspace& ws, const mpv_shape* s, int gemm) {
   BwdPlan pl;
   const int64_t L = s->L, S = s->S_local, B = s->B, z = s->z;
   const bool planes = gemm == MPV_GEMM_F16X3;
@@ -1357,19 +1357,11 @@ static BwdPlan plan_bwd(const mpv_shape* s, int gemm) {
   if (kc < 1) kc = 1;
   pl.dr_rows_per_chunk = (int)(cdiv(cdiv(rows, kc), kr) * kr);
   pl.nKc = (int)cdiv(rows, pl.dr_rows_per_chunk);
-  size_t off = 0;
-  auto carve = [&off](size_t bytes) {
-    const size_t at = off;
-    off += align_up(bytes, 256);
-    return at;
-  };
-  pl.coef_off = carve(sizeof(float) * 6 * (size_t)B * S);
-  pl.colpart_off = carve(sizeof(float) * (size_t)pl.nSc * 2 * B * L);
-  pl.slab_off = carve(sizeof(float) * (size_t)pl.nKc * L * z);
-  pl.bound_off = carve(sizeof(float) * ((size_t)B + 64));
-  // chunked: rows_pad rows of 2 * ldg halves
-  pl.planes_off = carve(planes ? 2 * sizeof(uint16_t) * (size_t)pl.rows_pad * pl.ldg : 0);
-  pl.end_off = off;
+  pl.coef = ws.take<float>(6, B, S);
+  pl.colpart = ws.take<float>(pl.nSc, 2, B, L);
+  pl.slab = ws.take<float>(pl.nKc, L, z);
+  pl.gbound = ws.take<float>(B + 64);
+  pl.g16 = ws.take<uint16_t>(planes ? 2 : 0, pl.rows_pad, pl.ldg);
   return pl;
 }
 
@@ -1387,7 +1379,7 @@ int64_t mpv_noise_plane_cols(const mpv_shape* shape) {
 
 size_t mpv_bwd_workspace_bytes(const mpv_shape* shape, int gemm) {
   if (check_shape(shape) != MPV_OK) return 0;
-  return plan_bwd(shape, gemm).total_bytes();
+  return layout_bytes(plan_bwd, shape, gemm);
 }
 
 int mpv_probit_bwd(const mpv_shape* shape, const mpv_bwd_args* a, void* stream) {
@@ -1398,7 +1390,8 @@ int mpv_probit_bwd(const mpv_shape* shape, const mpv_bwd_args* a, void* stream) 
   MPV_REQUIRE(a->gemm == MPV_GEMM_F32 || a->gemm == MPV_GEMM_F16X3, "unknown gemm mode %d",
               a->gemm);
   const bool planes = a->gemm == MPV_GEMM_F16X3;
-  const BwdPlan pl = plan_bwd(shape, a->gemm);
+  Workspace carve(a->workspace);
+  const BwdPlan pl = plan_bwd(carve, shape, a->gemm);
   MPV_REQUIRE(!(a->dR32 && a->dR64), "dR32 or dR64, not both");
   void* const dR_out = a->dR64 ? (void*)a->dR64 : (void*)a->dR32;
   const int dR_dtype = a->dR64 ? MPV_F64 : MPV_F32;
@@ -1419,16 +1412,9 @@ int mpv_probit_bwd(const mpv_shape* shape, const mpv_bwd_args* a, void* stream) 
       MPV_REQUIRE(a->eps != nullptr, "MPV_GEMM_F32 needs eps");
     }
   }
-  MPV_REQUIRE(a->workspace_bytes >= pl.total_bytes(), "workspace too small: %zu < %zu",
-              a->workspace_bytes, pl.total_bytes());
+  MPV_REQUIRE(carve.fits(a->workspace_bytes), "workspace too small: %zu < %zu",
+              a->workspace_bytes, carve.bytes());
   hipStream_t st = as_stream(stream);
-  char* ws = reinterpret_cast<char*>(a->workspace);
-  float* coef = reinterpret_cast<float*>(ws + pl.coef_off);
-  float* colpart = reinterpret_cast<float*>(ws + pl.colpart_off);
-  float* slab = reinterpret_cast<float*>(ws + pl.slab_off);
-  float* gbound = reinterpret_cast<float*>(ws + pl.bound_off);
-  // G planes, chunked: rows_pad rows of gld = 2 * ldg halves
-  uint16_t* g16 = reinterpret_cast<uint16_t*>(ws + pl.planes_off);
   const int64_t gld = 2 * pl.ldg;
   const int S = (int)shape->S_local, B = (int)shape->B, L = (int)shape->L, z = (int)shape->z;
   const bool want_planes = planes && dR_out != nullptr;
@@ -1440,21 +1426,20 @@ int mpv_probit_bwd(const mpv_shape* shape, const mpv_bwd_args* a, void* stream) 
     kl_blocks = (int)std::min<int64_t>(cdiv(kl.B * kl.d, kCoefThreads), 256);
   }
   MPV_LAUNCH("bwd_coef", bwd_coef_kernel, dim3(B + kl_blocks), dim3(kCoefThreads), 0, st, a->y, a->rowstat,
-             a->bstat, a->gscal, a->g_indiv, a->g_indiv_label, coef,
-             want_planes ? gbound : nullptr, S, B, L, (float)shape->S_total, a->nll_coeff,
+             a->bstat, a->gscal, a->g_indiv, a->g_indiv_label, pl.coef,
+             want_planes ? pl.gbound : nullptr, S, B, L, (float)shape->S_total, a->nll_coeff,
              a->c_coeff, a->live, kl, kl_blocks);
-  if (int rc = check_launch("bwd_coef")) return rc;
   if (want_planes) {
     const int64_t pad_rows = (int64_t)pl.rows_pad - (int64_t)B * S;
     if (pad_rows > 0) {
       const size_t off = (size_t)B * S * gld, n = (size_t)pad_rows * gld * sizeof(uint16_t);
-      if (hipMemsetAsync(g16 + off, 0, n, st) != hipSuccess)
+      if (hipMemsetAsync(pl.g16 + off, 0, n, st) != hipSuccess)
         return fail(MPV_ELAUNCH, "memset of G pad rows failed");
     }
   }
 
-  const ElemParams ep{a->y, a->fe_out, a->fx_out, a->g_indiv, a->g_indiv_label, coef, a->T,
-                      want_planes ? g16 : nullptr, gbound, gld, colpart, S, B, L,
+  const ElemParams ep{a->y, a->fe_out, a->fx_out, a->g_indiv, a->g_indiv_label, pl.coef, a->T,
+                      want_planes ? pl.g16 : nullptr, pl.gbound, gld, pl.colpart, S, B, L,
                       want_planes ? pl.Lc : L, (int)t_cols(L), pl.TPR, pl.RPI, pl.rows_per_chunk,
                       1.0f / (float)shape->S_total};
   const dim3 eg(B, pl.nSc, pl.nLc);
@@ -1465,26 +1450,24 @@ int mpv_probit_bwd(const mpv_shape* shape, const mpv_bwd_args* a, void* stream) 
     MPV_LAUNCH("bwd_elem", bwd_elem_kernel<true>, eg, dim3(256), 0, st, ep);
   else
     MPV_LAUNCH("bwd_elem", bwd_elem_kernel<false>, eg, dim3(256), 0, st, ep);
-  if (int rc = check_launch("bwd_elem")) return rc;
   if (!dR_out) {
-    if (int rc = launch_sum_slabs(colpart, pl.nSc, 2 * (int64_t)B * L, a->dfe_dfx, MPV_F32, st))
+    if (int rc = launch_sum_slabs(pl.colpart, pl.nSc, 2 * (int64_t)B * L, a->dfe_dfx, MPV_F32, st))
       return rc;
   }
 
   if (dR_out) {
     const dim3 grid((unsigned)((int64_t)pl.nLt * pl.nZt * pl.nKc)), block(pl.tile.threads);
-    const DrCommon dc{slab, S, B, L, z, pl.nLt, pl.nZt, pl.nKc, pl.dr_rows_per_chunk};
+    const DrCommon dc{pl.slab, S, B, L, z, pl.nLt, pl.nZt, pl.nKc, pl.dr_rows_per_chunk};
     if (planes) {
-      const Dr16Params dp{g16, gbound, gld, a->eps16, dc, pl.rows_pad};
+      const Dr16Params dp{pl.g16, pl.gbound, gld, a->eps16, dc, pl.rows_pad};
       MPV_LAUNCH("dR_gemm", pl.tile.kernel16, grid, block, 0, st, dp);
     } else {
       const DrParams dp{a->T, a->eps, dc, (int)t_cols(L)};
       MPV_LAUNCH("dR_gemm", pl.tile.kernel32, grid, block, 0, st, dp);
     }
-    if (int rc = check_launch("dR_gemm")) return rc;
     // the column partials (d fe_out, d fx_out) and the dR slabs in one launch
-    if (int rc = launch_sum_slabs_pair(colpart, pl.nSc, 2 * (int64_t)B * L, a->dfe_dfx, MPV_F32,
-                                       slab, pl.nKc, (int64_t)L * z, dR_out, dR_dtype, st))
+    if (int rc = launch_sum_slabs_pair(pl.colpart, pl.nSc, 2 * (int64_t)B * L, a->dfe_dfx, MPV_F32,
+                                       pl.slab, pl.nKc, (int64_t)L * z, dR_out, dR_dtype, st))
       return rc;
   }
   return MPV_OK;

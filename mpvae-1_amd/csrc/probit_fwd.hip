@@ -1751,7 +1751,6 @@ static FwdTile pick_fwd_tile(const mpv_shape* s, int gemm) {
 struct FwdPlan {
   FwdTile tile;
   int nNt, nSt, nSc, tps;
-  size_t rowpart_bytes, colpart_bytes;
 };
 
 static FwdPlan plan_fwd(const mpv_shape* s, int gemm) {
@@ -1770,13 +1769,49 @@ static FwdPlan plan_fwd(const mpv_shape* s, int gemm) {
   if (want > pl.nSt) want = pl.nSt;
   pl.tps = (int)cdiv(pl.nSt, want);
   pl.nSc = (int)cdiv(pl.nSt, pl.tps);
-  pl.rowpart_bytes = align_up(sizeof(float) * 6 * (size_t)pl.nNt * s->B * s->S_local, 256);
-  pl.colpart_bytes = pl.nSc > 1 ? align_up(sizeof(float) * (size_t)pl.nSc * 2 * s->B * s->L, 256) : 0;
   return pl;
 }
 
-static void launch_fwd(const FwdPlan& pl, dim3 grid, hipStream_t st, const FwdParams& p) {
-  MPV_LAUNCH("probit_fwd", pl.tile.kernel, grid, dim3(pl.tile.threads), 0, st, p);
+// The forward's workspace: the row partials, then the column partials of more
+// than one s-chunk (one chunk: the tiles write colsum itself).
+struct FwdWs {
+  float* rowpart;  // [6][nNt][B][S]
+  float* colpart;  // [nSc][2][B][L]
+};
+
+static FwdWs fwd_ws(Workspace& ws, const mpv_shape* s, const FwdPlan& pl) {
+  FwdWs w;
+  w.rowpart = ws.take<float>(6, pl.nNt, s->B, s->S_local);
+  w.colpart = ws.take<float>(pl.nSc > 1 ? pl.nSc : 0, 2, s->B, s->L);
+  return w;
+}
+
+// The prediction's: column partials [nSc][B][L] alone.
+static float* predict_ws(Workspace& ws, const mpv_shape* s, const FwdPlan& pl) {
+  return ws.take<float>(pl.nSc > 1 ? pl.nSc : 0, s->B, s->L);
+}
+
+// What a forward and a prediction launch planned as `pl` share of FwdParams,
+// from mpv_fwd_args or mpv_predict_args; y, fe, T, rowpart and colpart are the
+// caller's (NULL here).
+template <typename Args>
+static FwdParams fwd_params(const mpv_shape* shape, const FwdPlan& pl, const Args& a) {
+  FwdParams p{};
+  p.fx = a.fx_out;
+  p.R = a.R32;
+  p.eps = a.eps;
+  p.R16 = a.R16;
+  p.eps16 = a.eps16;
+  p.S = (int)shape->S_local;
+  p.B = (int)shape->B;
+  p.L = (int)shape->L;
+  p.ldT = (int)t_cols(shape->L);
+  p.z = (int)shape->z;
+  p.nNt = pl.nNt;
+  p.nSc = pl.nSc;
+  p.tps = pl.tps;
+  p.nSt = pl.nSt;
+  return p;
 }
 
 static int check_split_operand(const mpv_split16& o, int64_t rows, int64_t ld_min,
@@ -1800,9 +1835,18 @@ size_t mpv_fwd_workspace_bytes(const mpv_shape* shape) {
   if (check_shape(shape) != MPV_OK) return 0;
   size_t most = 0;  // enough for either GEMM mode's tiling
   for (int gemm : {MPV_GEMM_F16X3, MPV_GEMM_F32}) {
-    const FwdPlan pl = plan_fwd(shape, gemm);
-    most = std::max(most, pl.rowpart_bytes + pl.colpart_bytes);
+    const size_t need = layout_bytes(fwd_ws, shape, plan_fwd(shape, gemm));
+    if (need == 0) return 0;  // a layout that does not fit
+    most = std::max(most, need);
   }
+  return most;
+}
+
+size_t mpv_predict_workspace_bytes(const mpv_shape* shape) {
+  if (check_shape(shape) != MPV_OK) return 0;
+  size_t most = 0;  // enough for either GEMM mode's tiling
+  for (int gemm : {MPV_GEMM_F16X3, MPV_GEMM_F32})
+    most = std::max(most, layout_bytes(predict_ws, shape, plan_fwd(shape, gemm)));
   return most;
 }
 
@@ -1826,7 +1870,7 @@ static int launch_finalize(const mpv_shape* shape, const mpv_final_args& a, int 
   if (nb > 2048) nb = 2048;
   MPV_LAUNCH("finalize", finalize_kernel<SLOTS>, dim3((unsigned)(1 + nb)), dim3(kFinalThreads), 0,
              st, a, (int)shape->B, (int)shape->L, (float)shape->S_total, nslots, bstat_out);
-  return check_launch("finalize");
+  return MPV_OK;
 }
 
 // The GEMM operands of a forward or prediction launch planned as `pl`.
@@ -1846,12 +1890,11 @@ static int check_fwd_operands(const mpv_shape* shape, const FwdPlan& pl, int gem
   return MPV_OK;
 }
 
-// Bytes of the prediction's column partials [nSc][B][L] (0: the tiles write colsum).
-static size_t predict_colpart_bytes(const mpv_shape* s, const FwdPlan& pl) {
-  return pl.nSc > 1 ? align_up(sizeof(float) * (size_t)pl.nSc * s->B * s->L, 256) : 0;
-}
+}  // namespace mpv
 
-static int run_predict(const mpv_shape* shape, const mpv_predict_args* a, void* stream) {
+extern "C" {
+
+int mpv_probit_predict(const mpv_shape* shape, const mpv_predict_args* a, void* stream) {
   if (int rc = check_shape(shape)) return rc;
   MPV_REQUIRE(a != nullptr, "args is NULL");
   MPV_REQUIRE(a->fx_out && a->colsum, "NULL pointer in mpv_predict_args");
@@ -1860,35 +1903,17 @@ static int run_predict(const mpv_shape* shape, const mpv_predict_args* a, void* 
   // the full forward's plan: the same tile, nSc and tps
   const FwdPlan pl = plan_fwd(shape, a->gemm);
   if (int rc = check_fwd_operands(shape, pl, a->gemm, a->R32, a->eps, a->R16, a->eps16)) return rc;
-  const size_t need = predict_colpart_bytes(shape, pl);
-  MPV_REQUIRE(need == 0 || (a->workspace && a->workspace_bytes >= need),
-              "workspace too small: %zu < %zu", a->workspace ? a->workspace_bytes : (size_t)0, need);
+  Workspace carve(a->workspace);
+  float* const colpart = predict_ws(carve, shape, pl);
+  MPV_REQUIRE(pl.nSc == 1 || carve.fits(a->workspace_bytes), "workspace too small: %zu < %zu",
+              a->workspace ? a->workspace_bytes : (size_t)0, carve.bytes());
   const int64_t blocks = (int64_t)shape->B * pl.nSc * pl.nNt;
   MPV_REQUIRE(blocks < (int64_t(1) << 31), "grid too large");
   hipStream_t st = as_stream(stream);
-  FwdParams p;
-  p.y = nullptr;
-  p.fe = nullptr;
-  p.fx = a->fx_out;
-  p.R = a->R32;
-  p.eps = a->eps;
-  p.R16 = a->R16;
-  p.eps16 = a->eps16;
-  p.T = nullptr;
-  p.rowpart = nullptr;
-  p.colpart = pl.nSc > 1 ? reinterpret_cast<float*>(a->workspace) : a->colsum;
-  p.S = (int)shape->S_local;
-  p.B = (int)shape->B;
-  p.L = (int)shape->L;
-  p.ldT = (int)t_cols(shape->L);
-  p.z = (int)shape->z;
-  p.nNt = pl.nNt;
-  p.nSc = pl.nSc;
-  p.tps = pl.tps;
-  p.nSt = pl.nSt;
+  FwdParams p = fwd_params(shape, pl, *a);
+  p.colpart = pl.nSc > 1 ? colpart : a->colsum;
   MPV_LAUNCH("probit_predict", pl.tile.predict, dim3((unsigned)blocks), dim3(pl.tile.threads), 0,
              st, p);
-  if (int rc = check_launch("probit_predict")) return rc;
   if (pl.nSc == 1 && a->indiv_prob == nullptr && a->seed_advance == nullptr) return MPV_OK;
   // The order of the full forward's sum of the same shape's partials: its
   // buffer is (2, B, L), so launch_sum_slabs' split rule sees n = 2 B L.
@@ -1896,13 +1921,12 @@ static int run_predict(const mpv_shape* shape, const mpv_predict_args* a, void* 
   const int split = pl.nSc > kCombineFoldSlabs && slab_sum_is_split(pl.nSc, 2 * n);
   int64_t nb = cdiv(n, 256);
   if (nb > 2048) nb = 2048;
-  MPV_LAUNCH("predict_final", predict_final_kernel, dim3((unsigned)nb), dim3(256), 0, st,
-             pl.nSc > 1 ? p.colpart : nullptr, pl.nSc, split, n, a->colsum, a->indiv_prob,
-             (float)shape->S_total, a->seed_advance);
-  return check_launch("predict_final");
+  MPV_LAUNCH("predict_final", predict_final_kernel, dim3((unsigned)nb), dim3(256), 0, st, colpart,
+             pl.nSc, split, n, a->colsum, a->indiv_prob, (float)shape->S_total, a->seed_advance);
+  return MPV_OK;
 }
 
-static int run_fwd(const mpv_shape* shape, const mpv_fwd_args* a, void* stream) {
+int mpv_probit_fwd(const mpv_shape* shape, const mpv_fwd_args* a, void* stream) {
   if (int rc = check_shape(shape)) return rc;
   MPV_REQUIRE(a != nullptr, "args is NULL");
   MPV_REQUIRE(a->y && a->fe_out && a->fx_out && a->rowstat && a->bstat && a->colsum &&
@@ -1912,67 +1936,31 @@ static int run_fwd(const mpv_shape* shape, const mpv_fwd_args* a, void* stream) 
               a->gemm);
   const FwdPlan pl = plan_fwd(shape, a->gemm);
   if (int rc = check_fwd_operands(shape, pl, a->gemm, a->R32, a->eps, a->R16, a->eps16)) return rc;
-  const size_t need = pl.rowpart_bytes + pl.colpart_bytes;
-  MPV_REQUIRE(a->workspace_bytes >= need, "workspace too small: %zu < %zu", a->workspace_bytes,
-              need);
+  Workspace carve(a->workspace);
+  const FwdWs ws = fwd_ws(carve, shape, pl);
+  MPV_REQUIRE(carve.fits(a->workspace_bytes), "workspace too small: %zu < %zu", a->workspace_bytes,
+              carve.bytes());
   hipStream_t st = as_stream(stream);
-  FwdParams p;
+  FwdParams p = fwd_params(shape, pl, *a);
   p.y = a->y;
   p.fe = a->fe_out;
-  p.fx = a->fx_out;
-  p.R = a->R32;
-  p.eps = a->eps;
-  p.R16 = a->R16;
-  p.eps16 = a->eps16;
   p.T = a->T;
-  p.rowpart = reinterpret_cast<float*>(a->workspace);
-  p.colpart = pl.nSc > 1 ? reinterpret_cast<float*>((char*)a->workspace + pl.rowpart_bytes)
-                         : a->colsum;
-  p.S = (int)shape->S_local;
-  p.B = (int)shape->B;
-  p.L = (int)shape->L;
-  p.ldT = (int)t_cols(shape->L);
-  p.z = (int)shape->z;
-  p.nNt = pl.nNt;
-  p.nSc = pl.nSc;
-  p.tps = pl.tps;
-  p.nSt = pl.nSt;
+  p.rowpart = ws.rowpart;
+  p.colpart = pl.nSc > 1 ? ws.colpart : a->colsum;
   const int64_t blocks = (int64_t)shape->B * pl.nSc * pl.nNt;
   MPV_REQUIRE(blocks < (int64_t(1) << 31), "grid too large");
-  launch_fwd(pl, dim3((unsigned)blocks), st, p);
-  if (int rc = check_launch("probit_fwd")) return rc;
+  MPV_LAUNCH("probit_fwd", pl.tile.kernel, dim3((unsigned)blocks), dim3(pl.tile.threads), 0, st, p);
   // few s-chunks: fwd_combine sums the column partials too (one launch less);
   // many (small B, long S): the slab-sum kernel's split reduction
   const bool fold = pl.nSc > 1 && pl.nSc <= kCombineFoldSlabs;
   MPV_LAUNCH("fwd_combine", fwd_combine_kernel, dim3((unsigned)shape->B), dim3(kCombineThreads), 0,
              st, a->y, p.rowpart, a->rowstat, a->bstat, p.S, p.B, p.L, pl.nNt,
              fold ? p.colpart : nullptr, a->colsum, pl.nSc);
-  if (int rc = check_launch("fwd_combine")) return rc;
   if (pl.nSc > 1 && !fold) {
     if (int rc = launch_sum_slabs(p.colpart, pl.nSc, 2 * shape->B * shape->L, a->colsum, MPV_F32, st))
       return rc;
   }
   return MPV_OK;
-}
-
-}  // namespace mpv
-
-extern "C" {
-
-int mpv_probit_fwd(const mpv_shape* shape, const mpv_fwd_args* a, void* stream) {
-  return run_fwd(shape, a, stream);
-}
-
-size_t mpv_predict_workspace_bytes(const mpv_shape* shape) {
-  if (check_shape(shape) != MPV_OK) return 0;
-  size_t most = 0;  // enough for either GEMM mode's tiling
-  for (int gemm : {MPV_GEMM_F16X3, MPV_GEMM_F32})
-    most = std::max(most, predict_colpart_bytes(shape, plan_fwd(shape, gemm)));
-  return most;
-}
-
-int mpv_probit_predict(const mpv_shape* shape, const mpv_predict_args* a, void* stream) {
-  return run_predict(shape, a, stream);
 }
 
 int mpv_probit_finalize(const mpv_shape* shape, const mpv_final_args* a, void* stream) {

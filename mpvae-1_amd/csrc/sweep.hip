@@ -76,16 +76,22 @@ struct SweepThr {
   float v[MPV_MAX_THRESHOLDS];
 };
 
-// Workspace layout, shared by the host entry points and the kernels' callers.
+// Launch geometry and the workspace's pieces (NULL from the sizing pass).
 struct SweepPlan {
   int64_t N;
   int L, n_thr, chunks;
   int64_t rows_per_block, row_blocks, blocks;  // scan grid: blocks = row_blocks * chunks
   int64_t fin_rows, fin_blocks;                // row workgroups of sweep_reduce_kernel
-  size_t off_col, off_pk, off_tot, off_ef, off_xs, off_acc, off_nef, bytes;
+  uint64_t* rowword;
+  uint32_t* colpart;
+  int32_t* pkpart;
+  uint64_t* coltot;
+  double* ef_part;
+  int64_t* xs_part;
+  int32_t *acc_part, *nef_part;
 };
 
-static SweepPlan sweep_plan(int64_t N, int64_t L, int64_t n_thr) {
+static SweepPlan sweep_plan(Workspace& ws, int64_t N, int64_t L, int64_t n_thr) {
   SweepPlan p{};
   p.N = N;
   p.L = (int)L;
@@ -102,22 +108,14 @@ static SweepPlan sweep_plan(int64_t N, int64_t L, int64_t n_thr) {
   if (fb > kSweepRowBlocks) fb = kSweepRowBlocks;
   p.fin_rows = cdiv(N, fb);
   p.fin_blocks = cdiv(N, p.fin_rows);
-  size_t o = align_up(sizeof(uint64_t) * (size_t)N * (size_t)n_thr, 256);
-  p.off_col = o;
-  o += align_up(sizeof(uint32_t) * 64 * (size_t)(n_thr + 1) * (size_t)p.blocks, 256);
-  p.off_pk = o;
-  o += align_up(sizeof(int32_t) * 4 * (size_t)p.blocks, 256);
-  p.off_tot = o;
-  o += align_up(sizeof(uint64_t) * 64 * (size_t)(n_thr + 1) * (size_t)p.chunks, 256);
-  p.off_ef = o;
-  o += align_up(sizeof(double) * 64 * (size_t)p.fin_blocks, 256);
-  p.off_xs = o;
-  o += align_up(sizeof(int64_t) * 64 * (size_t)p.fin_blocks, 256);
-  p.off_acc = o;
-  o += align_up(sizeof(int32_t) * 64 * (size_t)p.fin_blocks, 256);
-  p.off_nef = o;
-  o += align_up(sizeof(int32_t) * 64 * (size_t)p.fin_blocks, 256);
-  p.bytes = o;
+  p.rowword = ws.take<uint64_t>(N, n_thr);
+  p.colpart = ws.take<uint32_t>(64, n_thr + 1, p.blocks);
+  p.pkpart = ws.take<int32_t>(4, p.blocks);
+  p.coltot = ws.take<uint64_t>(64, n_thr + 1, p.chunks);
+  p.ef_part = ws.take<double>(64, p.fin_blocks);
+  p.xs_part = ws.take<int64_t>(64, p.fin_blocks);
+  p.acc_part = ws.take<int32_t>(64, p.fin_blocks);
+  p.nef_part = ws.take<int32_t>(64, p.fin_blocks);
   return p;
 }
 
@@ -430,7 +428,7 @@ extern "C" {
 
 size_t mpv_sweep_workspace_bytes(int64_t N, int64_t L, int64_t n_thr) {
   if (!sweep_shape_ok(N, L) || n_thr < 1 || n_thr > MPV_MAX_THRESHOLDS) return 0;
-  return sweep_plan(N, L, n_thr).bytes;
+  return layout_bytes(sweep_plan, N, L, n_thr);
 }
 
 int mpv_threshold_sweep(const mpv_sweep_args* a, void* workspace, size_t workspace_bytes,
@@ -440,40 +438,29 @@ int mpv_threshold_sweep(const mpv_sweep_args* a, void* workspace, size_t workspa
               (long long)a->N, (long long)a->L, kSweepMaxL);
   MPV_REQUIRE(a->n_thr >= 1 && a->n_thr <= MPV_MAX_THRESHOLDS,
               "%lld thresholds: 1 .. %d per call", (long long)a->n_thr, MPV_MAX_THRESHOLDS);
-  const SweepPlan p = sweep_plan(a->N, a->L, a->n_thr);
-  MPV_REQUIRE(workspace && workspace_bytes >= p.bytes, "sweep workspace too small");
+  Workspace carve(workspace);
+  const SweepPlan p = sweep_plan(carve, a->N, a->L, a->n_thr);
+  MPV_REQUIRE(carve.fits(workspace_bytes), "sweep workspace too small");
   hipStream_t st = as_stream(stream);
-  char* ws = reinterpret_cast<char*>(workspace);
-  uint64_t* rowword = reinterpret_cast<uint64_t*>(ws);
-  uint32_t* colpart = reinterpret_cast<uint32_t*>(ws + p.off_col);
-  int32_t* pkpart = reinterpret_cast<int32_t*>(ws + p.off_pk);
-  uint64_t* coltot = reinterpret_cast<uint64_t*>(ws + p.off_tot);
-  double* ef_part = reinterpret_cast<double*>(ws + p.off_ef);
-  int64_t* xs_part = reinterpret_cast<int64_t*>(ws + p.off_xs);
-  int32_t* acc_part = reinterpret_cast<int32_t*>(ws + p.off_acc);
-  int32_t* nef_part = reinterpret_cast<int32_t*>(ws + p.off_nef);
   SweepThr thr{};
   for (int j = 0; j < p.n_thr; ++j) thr.v[j] = a->thr[j];
   if (p.chunks > 1) {
     const int64_t n = p.N * p.n_thr;
     const int64_t zb = cdiv(n, kSweepThreads * 8);
     MPV_LAUNCH("metric_sweep", sweep_zero_kernel, dim3((unsigned)(zb < 4096 ? zb : 4096)),
-               dim3(kSweepThreads), 0, st, rowword, n);
-    if (int rc = check_launch("sweep_zero")) return rc;
+               dim3(kSweepThreads), 0, st, p.rowword, n);
   }
   MPV_LAUNCH("metric_sweep", sweep_scan_kernel, dim3((unsigned)p.blocks), dim3(kSweepThreads), 0, st,
-             a->pred, a->target, p.N, p.L, p.n_thr, p.chunks, p.rows_per_block, thr, rowword,
-             colpart, pkpart);
-  if (int rc = check_launch("sweep_scan")) return rc;
+             a->pred, a->target, p.N, p.L, p.n_thr, p.chunks, p.rows_per_block, thr, p.rowword,
+             p.colpart, p.pkpart);
   const int64_t col_blocks = (int64_t)p.chunks * (p.n_thr + 1);
   MPV_LAUNCH("metric_sweep", sweep_reduce_kernel, dim3((unsigned)(p.fin_blocks + col_blocks)),
-             dim3(kRedThreads), 0, st, rowword, colpart, p.N, p.n_thr, p.chunks, p.row_blocks,
-             p.fin_rows, p.fin_blocks, ef_part, xs_part, acc_part, nef_part, coltot);
-  if (int rc = check_launch("sweep_reduce")) return rc;
+             dim3(kRedThreads), 0, st, p.rowword, p.colpart, p.N, p.n_thr, p.chunks, p.row_blocks,
+             p.fin_rows, p.fin_blocks, p.ef_part, p.xs_part, p.acc_part, p.nef_part, p.coltot);
   MPV_LAUNCH("metric_sweep", sweep_final_kernel, dim3((unsigned)p.n_thr), dim3(kSweepThreads), 0, st,
-             coltot, pkpart, ef_part, xs_part, acc_part, nef_part, p.N, p.L, p.n_thr, p.blocks,
-             p.fin_blocks, a->out);
-  return check_launch("sweep_final");
+             p.coltot, p.pkpart, p.ef_part, p.xs_part, p.acc_part, p.nef_part, p.N, p.L, p.n_thr,
+             p.blocks, p.fin_blocks, a->out);
+  return MPV_OK;
 }
 
 }  // extern "C"

@@ -647,9 +647,9 @@ static int noise_philox(float* eps, const mpv_shape* shape, uint64_t seed,
   const int threads = 256;
   const int64_t blocks = std::min<int64_t>(cdiv(nthreads, threads), int64_t(1) << 22);
   MPV_LAUNCH("noise_philox", noise_philox_kernel, dim3((unsigned)blocks), dim3(threads), 0,
-                     as_stream(stream), eps, e_begin, e_count, (uint32_t)seed,
-                     (uint32_t)(seed >> 32), offset, seed_dev);
-  return check_launch("noise_philox");
+             as_stream(stream), eps, e_begin, e_count, (uint32_t)seed,
+             (uint32_t)(seed >> 32), offset, seed_dev);
+  return MPV_OK;
 }
 
 int mpv_noise_philox(float* eps, const mpv_shape* shape, uint64_t seed, uint64_t offset,
@@ -666,8 +666,8 @@ int mpv_noise_philox_dev(float* eps, const mpv_shape* shape, const uint64_t* see
 int mpv_philox_raw(uint32_t* out, int64_t n, uint64_t ctr0, uint64_t key, void* stream) {
   MPV_REQUIRE(out != nullptr && n > 0, "bad philox_raw arguments");
   MPV_LAUNCH("philox_raw", philox_raw_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0,
-                     as_stream(stream), out, n, ctr0, (uint32_t)key, (uint32_t)(key >> 32));
-  return check_launch("philox_raw");
+             as_stream(stream), out, n, ctr0, (uint32_t)key, (uint32_t)(key >> 32));
+  return MPV_OK;
 }
 
 static int check_split(const mpv_split16* o) {
@@ -677,7 +677,12 @@ static int check_split(const mpv_split16* o) {
   return MPV_OK;
 }
 
-size_t mpv_split_workspace_bytes(void) { return sizeof(float) * kMaxBlocks; }
+// mpv_split_f16's workspace: the block maxima of maxabs_kernel.
+static float* split_ws(Workspace& ws) { return ws.take<float>(kMaxBlocks); }
+
+size_t mpv_split_workspace_bytes(void) {
+  return layout_bytes(split_ws);
+}
 
 int mpv_split_f16(const void* x, int x_dtype, int64_t rows, int64_t cols, const mpv_split16* out,
                   void* workspace, void* stream) {
@@ -689,16 +694,17 @@ int mpv_split_f16(const void* x, int x_dtype, int64_t rows, int64_t cols, const 
   const int64_t plane_elems = out->rows_pad * (out->ld / 2);
   const int64_t n = rows * cols;
   const bool aligned = (reinterpret_cast<uintptr_t>(x) & 15) == 0;
-  with_dtype(x_dtype, [&](auto t) {
+  Workspace carve(workspace);
+  float* const bmax = split_ws(carve);
+  return with_dtype(x_dtype, [&](auto t) -> int {
     typedef decltype(t) T;
     const T* xt = reinterpret_cast<const T*>(x);
     const dim3 b(256);
     if (n <= kSplitSmall && plane_elems < (int64_t(1) << 31)) {
       const dim3 g((unsigned)std::min<int64_t>(cdiv(plane_elems, 256 * 4), 256));
       MPV_LAUNCH("split", split_small_kernel<T>, g, b, 0, s, xt, (int)rows, (int)cols, *out);
-      return;
+      return MPV_OK;
     }
-    float* bmax = reinterpret_cast<float*>(workspace);
     const unsigned g = grid_for(n, 256, kSplitMaxBlocks);
     if (aligned)
       MPV_LAUNCH("split", (maxabs_kernel<T, 16 / sizeof(T)>), dim3(g), b, 0, s, xt, n, bmax);
@@ -710,8 +716,8 @@ int mpv_split_f16(const void* x, int x_dtype, int64_t rows, int64_t cols, const 
     else
       MPV_LAUNCH("split", (split_kernel<T, 1>), dim3(grid_for(plane_elems, 256, 16384)), b, 0, s,
                  xt, rows, cols, *out, bmax, (int)g);
+    return MPV_OK;
   });
-  return check_launch("split_f16");
 }
 
 static int noise_philox_f16(const mpv_shape* shape, uint64_t seed, const uint64_t* seed_dev,
@@ -740,7 +746,7 @@ static int noise_philox_f16(const mpv_shape* shape, uint64_t seed, const uint64_
   MPV_LAUNCH("noise_philox", noise_philox16_kernel, dim3((unsigned)nb), dim3(threads), 0, s, *out,
              (int)shape->S_local, (int)shape->B, (int)shape->z, shape->s_offset, (uint32_t)seed,
              (uint32_t)(seed >> 32), offset, (int)rows, rpb, seed_dev, ss);
-  return check_launch("noise_philox_f16");
+  return MPV_OK;
 }
 
 int mpv_noise_philox_f16(const mpv_shape* shape, uint64_t seed, uint64_t offset,
@@ -776,23 +782,23 @@ int mpv_convert(const void* src, int sd, void* dst, int dd, int64_t n, void* str
   if (n == 0) return MPV_OK;
   const unsigned g = grid_for(n, 256);
   hipStream_t s = as_stream(stream);
-  with_dtype(sd, [&](auto from) {
-    with_dtype(dd, [&](auto to) {
+  return with_dtype(sd, [&](auto from) {
+    return with_dtype(dd, [&](auto to) -> int {
       typedef decltype(from) S;
       typedef decltype(to) D;
       MPV_LAUNCH("convert", (convert_kernel<S, D>), dim3(g), dim3(256), 0, s,
                  reinterpret_cast<const S*>(src), reinterpret_cast<D*>(dst), n);
+      return MPV_OK;
     });
   });
-  return check_launch("convert");
 }
 
 int mpv_bstat_combine(const float* gathered, int64_t nshards, int64_t B, float* out,
                       void* stream) {
   MPV_REQUIRE(gathered && out && nshards > 0 && B > 0, "bad bstat_combine arguments");
   MPV_LAUNCH("bstat_combine", bstat_combine_kernel, dim3((unsigned)cdiv(B, 256)), dim3(256), 0,
-                     as_stream(stream), gathered, nshards, B, out);
-  return check_launch("bstat_combine");
+             as_stream(stream), gathered, nshards, B, out);
+  return MPV_OK;
 }
 
 int mpv_reparam_fwd(const mpv_reparam_args* a, void* stream) {
@@ -802,8 +808,8 @@ int mpv_reparam_fwd(const mpv_reparam_args* a, void* stream) {
   const int64_t n = a->n_e + a->n_x;
   if (n == 0) return MPV_OK;
   MPV_LAUNCH("reparam_fwd", reparam_fwd_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0,
-                     as_stream(stream), *a);
-  return check_launch("reparam_fwd");
+             as_stream(stream), *a);
+  return MPV_OK;
 }
 
 int mpv_reparam_bwd(const mpv_reparam_bwd_args* a, void* stream) {
@@ -815,8 +821,8 @@ int mpv_reparam_bwd(const mpv_reparam_bwd_args* a, void* stream) {
   const int64_t n = a->n_e + a->n_x;
   if (n == 0) return MPV_OK;
   MPV_LAUNCH("reparam_bwd", reparam_bwd_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0,
-                     as_stream(stream), *a);
-  return check_launch("reparam_bwd");
+             as_stream(stream), *a);
+  return MPV_OK;
 }
 
 int mpv_kl_bwd(const mpv_kl_bwd_args* a, void* stream) {
@@ -825,8 +831,8 @@ int mpv_kl_bwd(const mpv_kl_bwd_args* a, void* stream) {
               "bad kl_bwd arguments");
   MPV_REQUIRE(a->B > 0 && a->d > 0, "bad kl_bwd sizes");
   MPV_LAUNCH("kl_bwd", kl_bwd_kernel, dim3(grid_for(a->B * a->d, 256, 4096)), dim3(256), 0,
-                     as_stream(stream), *a);
-  return check_launch("kl_bwd");
+             as_stream(stream), *a);
+  return MPV_OK;
 }
 
 }  // extern "C"
@@ -856,7 +862,7 @@ static int launch_slab_pair(const SlabSum& a, const SlabSum& b, hipStream_t s) {
   MPV_REQUIRE(a.blocks + b.blocks < (int64_t(1) << 31), "slab sums too large");
   MPV_LAUNCH("sum_slabs", sum_slabs_kernel, dim3((unsigned)(a.blocks + b.blocks)), dim3(1024), 0,
              s, a, b);
-  return check_launch("sum_slabs");
+  return MPV_OK;
 }
 
 int launch_sum_slabs_pair(const float* in0, int64_t nslab0, int64_t n0, void* out0,
@@ -875,6 +881,6 @@ int launch_sum_slabs(const float* in, int64_t nslab, int64_t n, void* out, int o
   q.blocks = cdiv(n, kSlabSingleThreads);
   MPV_LAUNCH("sum_slabs", sum_slabs_plain_kernel, dim3((unsigned)std::min<int64_t>(q.blocks, 8192)),
              dim3(kSlabSingleThreads), 0, s, q);
-  return check_launch("sum_slabs");
+  return MPV_OK;
 }
 }  // namespace mpv

@@ -134,3 +134,25 @@ def test_host_library_exports_what_its_header_declares():
     assert set(re.findall(r"\bT (mpvh_\w+)", out)) == set(declared)
     assert lib.mpvh_probit_fwd(H.Shape(0, 4, 0, 2, 8, 8), mpvae_host.FwdArgs()) == 1
     assert b"bad shape" in lib.mpvh_last_error()
+
+
+def test_timing_tags_are_the_kernels_table():
+    """Every launch in csrc/ goes through MPV_LAUNCH, whose first argument is the
+    timing tag: the tags are mpvae_hip.KERNELS, no more and no fewer.  The label
+    weights' shared launcher takes its tag from its three callers."""
+    csrc = os.path.join(ROOT, "mpvae-1_amd", "csrc")
+    tags, passed_on = set(), 0
+    for name in sorted(n for n in os.listdir(csrc) if n.endswith(".hip")):
+        src = open(os.path.join(csrc, name)).read()
+        assert "hipLaunchKernelGGL" not in src and "<<<" not in src, name
+        assert not re.search(r"check_launch\(\s*\"", src), name
+        for first in re.findall(r"MPV_LAUNCH\(\s*(\"\w+\"|\w+)", src):
+            if first.startswith('"'):
+                tags.add(first.strip('"'))
+            else:
+                assert first == "tag" and name == "fairness.hip", (name, first)
+                passed_on += 1
+        tags.update(re.findall(r"launch_row_weights<[^;]*?>\(\s*\"(\w+)\"", src))
+    assert passed_on == 1
+    assert tags == set(H.KERNELS)
+    assert len(H.KERNELS) == len(set(H.KERNELS))

@@ -52,6 +52,7 @@ from test_gpu_bwd_lattice import LATTICE_SHAPES, W, lattice_inputs
 from test_gpu_calib import BY as CALIB_GOLDEN, EDGES as CALIB_EDGES, _edge_case
 from test_gpu_curves import _seeded
 from test_gpu_dr_edges import CASES as DR_CASES, case_inputs as dr_case_inputs, dr_stages
+from test_gpu_eval import make_case as eval_case
 from test_gpu_predict import SHAPES as PREDICT_SHAPES, _args as predict_args, _case as predict_case
 
 pytestmark = pytest.mark.gpu
@@ -198,7 +199,8 @@ TEST_MODE_MIN = {"f16x3": 18, "f32": 13}
 
 
 @pytest.mark.parametrize("gemm", ["f16x3", "f32"])
-@pytest.mark.parametrize("L,z,B,S,d", [LATTICE_SHAPES[0], TILE_WALKS[2]])
+@pytest.mark.parametrize("L,z,B,S,d", [LATTICE_SHAPES[0], TILE_WALKS[2],
+                                       (38, 38, 2, 2000, 8)])  # 8 / 16 s-chunks: column partials
 def test_elbo_test_mode_forward(L, z, B, S, d, gemm, monkeypatch):
     inp, noise, g_I, g_IL = lattice_inputs(L, z, B, S, d, L * 7 + S)
     _both(monkeypatch, [mpvae_ops],
@@ -554,6 +556,24 @@ def test_calibration(name, monkeypatch):
                 "contributed": contributed, "g_threshold": x.grad, "g_p": p.grad}
 
     _both(monkeypatch, [mpvae_fair], run, 10 if T else 9, f"calibration {name}")
+
+
+# counts, out, terms, ws; with definitions out_defs too
+@pytest.mark.parametrize("D", [None, 2], ids=["one_definition", "two_definitions"])
+def test_split_eval(D, monkeypatch):
+    """mpv_split_eval and mpv_split_eval_defs at N 24, L 257, G 3, R 2 with 5
+    targets a definition (past the register tile of 4): every piece of the
+    workspace is non-empty."""
+    c = eval_case(L=257, N=24, G=3, T=5 * (D or 1), R=2)
+
+    def run(alloc):
+        order, goff = mpvae_fair._group_layout(_dev(c["gid"].astype(np.int32)), c["G"])
+        res = mpvae_fair._split_eval(alloc(_dev(c["pred"])), alloc(_dev(c["y"])),
+                                     alloc(_dev(c["w"])), alloc(order), alloc(goff), c["G"],
+                                     c["R"], D)
+        return dict(zip(("counts", "out", "terms", "out_defs"), res))
+
+    _both(monkeypatch, [mpvae_fair], run, 4 if D is None else 5, f"split eval D={D}")
 
 
 # ====================================================================== Adam
