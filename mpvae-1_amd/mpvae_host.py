@@ -23,43 +23,15 @@ from mpvae_ops import ShardBackend, stat_buffers
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MPVAE_HOST_LIB", os.path.join(HERE, "libmpvae_host.so"))
-ABI_VERSION = 2
-vp = ctypes.c_void_p
 F32, F64 = torch.float32, torch.float64
 
-
-class FwdArgs(ctypes.Structure):
-    _fields_ = [("y", vp), ("fe_out", vp), ("fx_out", vp), ("R", vp), ("R_dtype", ctypes.c_int),
-                ("eps", vp), ("T", vp), ("rowstat", vp), ("bstat", vp), ("colsum", vp)]
-
-
-class FinalArgs(ctypes.Structure):
-    _fields_ = [("bstat", vp), ("colsum", vp), ("fe_mu", vp), ("fe_logvar", vp), ("fx_mu", vp),
-                ("fx_logvar", vp), ("d", ctypes.c_int64), ("nll_coeff", ctypes.c_float),
-                ("c_coeff", ctypes.c_float), ("out6", vp), ("indiv_prob", vp),
-                ("indiv_prob_label", vp)]
-
-
-class BwdArgs(ctypes.Structure):
-    _fields_ = [("y", vp), ("fe_out", vp), ("fx_out", vp), ("eps", vp), ("T", vp),
-                ("rowstat", vp), ("bstat", vp), ("gscal", vp), ("live", ctypes.c_int),
-                ("g_indiv", vp), ("g_indiv_label", vp), ("nll_coeff", ctypes.c_float),
-                ("c_coeff", ctypes.c_float), ("dfe_dfx", vp), ("dR", vp)]
-
-
-_SIGS = {
-    "mpvh_abi_version": (ctypes.c_int, []),
-    "mpvh_last_error": (ctypes.c_char_p, []),
-    "mpvh_set_threads": (ctypes.c_int, [ctypes.c_int]),
-    "mpvh_probit_fwd": (ctypes.c_int, [ctypes.POINTER(H.Shape), ctypes.POINTER(FwdArgs)]),
-    "mpvh_probit_predict": (ctypes.c_int, [ctypes.POINTER(H.Shape), vp, vp, ctypes.c_int, vp, vp]),
-    "mpvh_bstat_combine": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.c_int64, vp]),
-    "mpvh_probit_finalize": (ctypes.c_int, [ctypes.POINTER(H.Shape), ctypes.POINTER(FinalArgs)]),
-    "mpvh_probit_bwd": (ctypes.c_int, [ctypes.POINTER(H.Shape), ctypes.POINTER(BwdArgs)]),
-    "mpvh_kl_bwd": (ctypes.c_int, [vp, vp, vp, vp, ctypes.c_int64, ctypes.c_int64, vp, ctypes.c_int,
-                                   vp, vp, vp, vp]),
-}
+_header = H.read_header("mpvae_host.h", {"mpv_shape": H.Shape})
+STRUCTS, _SIGS = _header.structs, _header.prototypes
 EXPORTS = sorted(_SIGS)
+ABI_VERSION = _header.constants["MPVH_ABI_VERSION"]
+FwdArgs = STRUCTS["mpvh_fwd_args"]
+FinalArgs = STRUCTS["mpvh_final_args"]
+BwdArgs = STRUCTS["mpvh_bwd_args"]
 
 _lib = None
 

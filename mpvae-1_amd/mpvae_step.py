@@ -31,6 +31,8 @@ import functools
 
 import torch
 
+import mpvae_hip as H
+
 
 def has_finite_grad(model):
     """fairsoft_utils.py:28-41 with one host sync: True iff every existing
@@ -92,7 +94,6 @@ def adam_step(opt, found_inf, updates=None, sched=None):
     and ``sched`` (a DeviceStepLR, or None) takes the scheduler step the
     reference takes after an applied update (fairsoft_train.py:142-146), both
     in the finish launch."""
-    import mpvae_hip as H
     lib = H.load_library()
     all_steps = []
     for gi, g in enumerate(opt.param_groups):
@@ -305,8 +306,8 @@ def _eval_mode(model):
         model.train(was_training)
 
 
-_SPLIT_ELEMS = {torch.float32: 0, torch.float64: 1, torch.int32: 2, torch.int64: 3,
-                torch.uint8: 4}  # dtype -> mpv_elem
+_SPLIT_ELEMS = {torch.float32: H.EL_F32, torch.float64: H.EL_F64, torch.int32: H.EL_I32,
+                torch.int64: H.EL_I64, torch.uint8: H.EL_U8}  # dtype -> mpv_elem
 
 
 class DeviceSplit:
@@ -434,7 +435,6 @@ class DeviceSplit:
             raise ValueError("out must hold one contiguous (B, cols) tensor per source, on the "
                              "split's device: label fp32, feat fp32, sens in its own dtype")
         if self.device.type == "cuda":
-            import mpvae_hip as H
             a = H.GatherArgs(n_sources=len(src), n_rows=self.n_rows, idx=H.ptr(idx),
                              n_idx=int(n_idx), B=B, start=int(start), pos=H.ptr(pos),
                              advance=int(bool(advance)), bad=H.ptr(self.bad))

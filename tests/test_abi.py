@@ -3,6 +3,7 @@
 import ctypes
 import os
 import re
+import shutil
 import subprocess
 
 import pytest
@@ -156,3 +157,62 @@ def test_timing_tags_are_the_kernels_table():
     assert passed_on == 1
     assert tags == set(H.KERNELS)
     assert len(H.KERNELS) == len(set(H.KERNELS))
+
+
+def _uncommented(path):
+    return re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
+
+
+def _bindings():
+    """(header path, {C name: ctypes class}, {function: (restype, argtypes)}) per header."""
+    import mpvae_host
+    return [(HEADER, H.STRUCTS, H.SIGNATURES),
+            (HOST_HEADER, mpvae_host.STRUCTS, dict(mpvae_host._SIGS))]
+
+
+def compile_layout_asserts(structs, headers, tmp_path):
+    """One _Static_assert per sizeof and per field offset of `structs`, with the
+    numbers of the ctypes classes, checked by the host C compiler against the
+    headers themselves.  Returns the compiler's CompletedProcess."""
+    rocm_clang = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "clang")
+    cc = shutil.which("cc") or (rocm_clang if os.path.exists(rocm_clang) else None)
+    if cc is None:
+        pytest.skip("no C compiler (cc, or ROCm's clang)")
+    lines = ["#include <stddef.h>"] + [f'#include "{os.path.basename(h)}"' for h in headers]
+    for name, cls in structs.items():
+        lines.append(f'_Static_assert(sizeof({name}) == {ctypes.sizeof(cls)}, "sizeof {name}");')
+        lines += [f'_Static_assert(offsetof({name}, {f}) == {getattr(cls, f).offset}, '
+                  f'"offsetof {name}.{f}");' for f, _ in cls._fields_]
+    src = tmp_path / "abi_layout.c"
+    src.write_text("\n".join(lines) + "\n")
+    return subprocess.run([cc, "-fsyntax-only", "-std=c11", "-I", os.path.dirname(HEADER),
+                           str(src)], capture_output=True, text=True)
+
+
+def test_derived_layouts_are_the_compilers(tmp_path):
+    """The ctypes classes the binding derives from the headers (cabi.py) have the
+    C compiler's sizeof and offsetof for every struct and field, the headers'
+    field names in the headers' order, and one argtype per declared parameter
+    (names and counts taken here by regex, not from the parser)."""
+    structs = {}
+    for header, classes, sigs in _bindings():
+        src = _uncommented(header)
+        bodies = re.findall(r"typedef\s+struct\s+(\w+)\s*\{(.*?)\}\s*\1\s*;", src, flags=re.S)
+        assert [n for n, _ in bodies] == list(classes)
+        for name, body in bodies:
+            declared = [re.search(r"(\w+)\s*(?:\[\w+\])?\s*$", d).group(1)
+                        for decl in body.split(";") if decl.strip() for d in decl.split(",")]
+            assert [f for f, _ in classes[name]._fields_] == declared, name
+        params = dict(re.findall(r"\b(mpvh?_[a-z0-9_]+)\s*\(([^()]*)\)", src))
+        assert sorted(params) == sorted(sigs)
+        for fn, text in params.items():
+            count = 0 if text.strip() == "void" else text.count(",") + 1
+            assert len(sigs[fn][1]) == count, fn
+        structs.update(classes)
+    done = compile_layout_asserts(structs, [HEADER, HOST_HEADER], tmp_path)
+    assert done.returncode == 0, done.stderr
+
+
+def test_missing_header_fails_loudly():
+    with pytest.raises(H.MPVError, match="nope.h not found"):
+        H.read_header("nope.h")
