@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MPV_ABI_VERSION 18 /* 4: device-memory Philox keys (mpv_noise_philox*_dev);
+#define MPV_ABI_VERSION 19 /* 4: device-memory Philox keys (mpv_noise_philox*_dev);
                               5: T rows padded to roundup(L, 4) floats;
                               6: mpv_linear (the VAE's Linear layers); mpv_bwd_args
                                  dR64 and kl;
@@ -67,7 +67,10 @@ extern "C" {
                                  weight definitions in one pass)
                              18: mpv_gather_batch (a batch gathered from a
                                  device-resident split at a device cursor);
-                                 MPV_EL_U8 */
+                                 MPV_EL_U8
+                             19: mpv_r_uniform_philox (the per-step random
+                                 r_sqrt_sigma of residue_sigma == "random",
+                                 drawn on the device) */
 
 enum mpv_status { MPV_OK = 0, MPV_EINVAL = 1, MPV_ELAUNCH = 2 };
 enum mpv_dtype { MPV_F32 = 0, MPV_F64 = 1 };
@@ -106,6 +109,30 @@ int mpv_noise_philox_dev(float* eps, const mpv_shape* shape, const uint64_t* see
 /* Raw Philox4x32-10 words (known-answer tests): out[4*i..4*i+3] =
  * philox(counter = ctr0 + i (as lo,hi,0,0), key = key). */
 int mpv_philox_raw(uint32_t* out, int64_t n, uint64_t ctr0, uint64_t key, void* stream);
+
+/* Replaces the per-step host draw of residue_sigma == "random"
+ * (fairsoft_train.py:60-66, :247-253; fairsoft_train_postprocess.py:97-103;
+ * train.py:120, :351): r_sqrt_sigma = np.random.uniform(-bound, bound, (L, z)),
+ * drawn on the device from the probit noise's key.  out is (L, z) fp64,
+ * contiguous.  Element e = l * z + k is double (e mod 2) of Philox4x32-10
+ * counter g = (e div 2 + offset) mod 2^64 with counter words (lo32(g),
+ * hi32(g), 1, 0) -- the noise entry points pass 0 as the third word, so under
+ * one key the two streams are disjoint -- and key `seed`, or the 64-bit word
+ * read from seed_dev at run time when that is not NULL (read only: the
+ * finalize launch of the same step advances it afterwards, in stream order).
+ * Double j of a counter is numpy's random_sample of its words (w_2j, w_2j+1):
+ *   u = ((w_2j >> 5) * 2^26 + (w_2j+1 >> 6)) * 2^-53
+ * and the value numpy's uniform, r = (-bound) + (bound - (-bound)) * u, the
+ * multiply and the add each rounded (no FMA): RandomState.uniform(-bound,
+ * bound)'s bits for the same words.  One thread per counter in workgroups of
+ * MPV_R_UNIFORM_THREADS, at most MPV_R_UNIFORM_MAX_BLOCKS of them striding
+ * over the counters; plain stores, no workspace, no atomics.  Supported:
+ * 1 <= L, z with L * z < 2^40, out not NULL, bound finite and > 0; anything
+ * else is MPV_EINVAL and launches nothing. */
+#define MPV_R_UNIFORM_THREADS 256
+#define MPV_R_UNIFORM_MAX_BLOCKS 1024
+int mpv_r_uniform_philox(int64_t L, int64_t z, double bound, uint64_t seed,
+                         const uint64_t* seed_dev, uint64_t offset, double* out, void* stream);
 
 /* 3xf16 split operand of the noise GEMMs: value = (hi + lo) / *scale, with hi
  * and lo fp16 values, zero padded, and *scale a power of two chosen on the
@@ -481,7 +508,7 @@ int mpv_adam_finish(const mpv_adam_finish_args* args, void* stream);
  * mpv_threshold_sweep), calib_fwd, calib_tables, calib_bwd, probit_predict,
  * predict_final (the two launches of mpv_probit_predict), split_eval, split_final
  * (the two launches of mpv_split_eval and of mpv_split_eval_defs), gather_batch (the
- * gather of mpv_gather_batch and its cursor launch).  Query synchronises the recorded events. */
+ * gather of mpv_gather_batch and its cursor launch), r_uniform (mpv_r_uniform_philox).  Query synchronises the recorded events. */
 int mpv_timing_enable(int on);
 int mpv_timing_reset(void);
 int mpv_timing_query(const char* kernel, int64_t* launches, double* total_ms);

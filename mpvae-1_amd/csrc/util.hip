@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <cmath>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -127,6 +128,51 @@ __global__ void philox_raw_kernel(uint32_t* out, int64_t n, uint64_t ctr0, uint3
   out[4 * i + 1] = w.y;
   out[4 * i + 2] = w.z;
   out[4 * i + 3] = w.w;
+}
+
+// ------------------------------------------------- random r_sqrt_sigma draw
+// U(-bound, bound) in fp64 (mpv_r_uniform_philox): one thread = one Philox
+// counter = two consecutive doubles.  The counter's third word is 1 where the
+// noise kernels above pass 0, so under one key the two streams never meet.
+// A double is numpy's random_sample of a word pair, (a >> 5, b >> 6) -> (a
+// 2^26 + b) 2^-53 (exact in fp64), and the value numpy's uniform, low + (high -
+// low) u: the multiply and the add each rounded (fp contract off below).
+MPV_DEV double r_uniform_value(uint32_t wa, uint32_t wb, double low, double range) {
+#pragma clang fp contract(off)
+  const double u = ((double)(wa >> 5) * 67108864.0 + (double)(wb >> 6)) * (1.0 / 9007199254740992.0);
+  const double scaled = range * u;
+  return low + scaled;
+}
+
+typedef double f64x2 __attribute__((ext_vector_type(2)));
+
+// VEC: out is 16-B aligned, a counter's two doubles go out as one 16-B store.
+template <bool VEC>
+__global__ __launch_bounds__(MPV_R_UNIFORM_THREADS) void r_uniform_kernel(
+    double* __restrict__ out, int64_t n, double bound, uint32_t k0, uint32_t k1, uint64_t offset,
+    const uint64_t* __restrict__ seed_dev) {
+#pragma clang fp contract(off)
+  philox_key(seed_dev, k0, k1);
+  const double low = -bound, range = bound - low;
+  const int64_t counters = (n + 1) >> 1;  // an odd n: the last counter gives one value
+  for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < counters;
+       g += (int64_t)gridDim.x * blockDim.x) {
+    const uint64_t ctr = (uint64_t)g + offset;
+    const u32x4 w = philox4x32_10(u32x4{(uint32_t)ctr, (uint32_t)(ctr >> 32), 1u, 0u}, k0, k1);
+    const double r0 = r_uniform_value(w.x, w.y, low, range);
+    const double r1 = r_uniform_value(w.z, w.w, low, range);
+    const int64_t e = g << 1;
+    if (e + 1 < n) {
+      if constexpr (VEC) {
+        *reinterpret_cast<f64x2*>(out + e) = f64x2{r0, r1};
+      } else {
+        out[e] = r0;
+        out[e + 1] = r1;
+      }
+    } else {
+      out[e] = r0;
+    }
+  }
 }
 
 // ------------------------------------------------------------- conversions
@@ -773,6 +819,28 @@ int mpv_noise_philox_f16_split(const mpv_shape* shape, uint64_t seed, const uint
   MPV_REQUIRE(x_dtype == MPV_F32 || x_dtype == MPV_F64, "unsupported dtype %d", x_dtype);
   SmallSplit ss{x, x_dtype, (int)rows, (int)cols, *x_out, 0};
   return noise_philox_f16(shape, seed, seed_dev, offset, out, stream, ss);
+}
+
+int mpv_r_uniform_philox(int64_t L, int64_t z, double bound, uint64_t seed,
+                         const uint64_t* seed_dev, uint64_t offset, double* out, void* stream) {
+  constexpr int64_t kMaxElems = int64_t(1) << 40;
+  MPV_REQUIRE(out != nullptr, "out is NULL");
+  MPV_REQUIRE(L >= 1 && z >= 1 && L < kMaxElems && z < kMaxElems && L <= (kMaxElems - 1) / z,
+              "mpv_r_uniform_philox needs 1 <= L, z and L * z < 2^40 (got %lld, %lld)",
+              (long long)L, (long long)z);
+  MPV_REQUIRE(std::isfinite(bound) && bound > 0.0, "bound must be finite and positive (got %g)",
+              bound);
+  const int64_t n = L * z;
+  const dim3 g(grid_for((n + 1) >> 1, MPV_R_UNIFORM_THREADS, MPV_R_UNIFORM_MAX_BLOCKS));
+  const dim3 b(MPV_R_UNIFORM_THREADS);
+  hipStream_t s = as_stream(stream);
+  if ((reinterpret_cast<uintptr_t>(out) & 15) == 0)
+    MPV_LAUNCH("r_uniform", r_uniform_kernel<true>, g, b, 0, s, out, n, bound, (uint32_t)seed,
+               (uint32_t)(seed >> 32), offset, seed_dev);
+  else
+    MPV_LAUNCH("r_uniform", r_uniform_kernel<false>, g, b, 0, s, out, n, bound, (uint32_t)seed,
+               (uint32_t)(seed >> 32), offset, seed_dev);
+  return MPV_OK;
 }
 
 int mpv_convert(const void* src, int sd, void* dst, int dd, int64_t n, void* stream) {

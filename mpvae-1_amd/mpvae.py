@@ -8,12 +8,16 @@ Same public names, signatures, parameter names, shapes and dtypes:
                                        indiv_prob, indiv_prob_label)
                                   reference mpvae.py:145-210
 
-and one name the reference lacks:
+and two names the reference lacks:
 
   predict_proba(fx_out, r_sqrt_sigma, args) -> indiv_prob
                                   compute_loss(...)[6] alone, without labels
                                   (mpvae.py:180, 203); VAE.predict_proba(feature,
                                   args) runs the feature branch first
+  draw_r_sqrt_sigma(args, device, out=None) -> r_sqrt_sigma
+                                  the per-step draw of residue_sigma == "random"
+                                  (fairsoft_train.py:60-66), on the host as the
+                                  reference or on the device
 
 Put ``mpvae-1_amd/`` on ``sys.path`` and ``from mpvae import VAE, compute_loss``
 works unchanged in the reference's training loop (fairsoft_train.py:57-146).
@@ -40,6 +44,11 @@ Build-only knobs read from ``args`` (defaults reproduce the reference):
                their ReLU and scale_coeff) on the fp32 matrix cores
                (mpvae_linear.py, csrc/linear.hip); "torch": nn.Linear
                (hipBLASLt / rocBLAS), for A/B.
+  mpvae_r_draw None (default) | "numpy" | "philox": the source of the fresh
+               r_sqrt_sigma the reference's loops draw every step under
+               residue_sigma == "random" (draw_r_sqrt_sigma below; the step
+               classes of mpvae_step draw with it; compute_loss itself takes
+               whatever r_sqrt_sigma it is given).
 """
 import numpy as np
 import torch
@@ -49,9 +58,10 @@ import torch.nn.functional as F
 import mpvae_hip
 import mpvae_dist
 import mpvae_linear
-from mpvae_ops import ElboConfig, FusedReparam, ProbitELBO, SingleReparam, probit_predict
+from mpvae_ops import (ElboConfig, FusedReparam, HipShardBackend, ProbitELBO, SingleReparam,
+                       probit_predict)
 
-__all__ = ["VAE", "compute_loss", "predict_proba"]
+__all__ = ["VAE", "compute_loss", "predict_proba", "draw_r_sqrt_sigma"]
 
 # the encoders' dropout backward folded into mpv_linear (same values; False:
 # nn.Dropout's own backward kernel, for A/B)
@@ -83,6 +93,61 @@ def _init_r_sqrt_sigma(args):
         return nn.Parameter(torch.zeros((L, z)), requires_grad=False)
     draw = torch.from_numpy(np.random.uniform(-bound, bound, (L, z)))
     return nn.Parameter(draw, requires_grad=args.residue_sigma != "random")
+
+
+R_DRAWS = ("numpy", "philox")  # args.mpvae_r_draw (None / absent: no per-step draw)
+
+
+def draw_r_sqrt_sigma(args, device, out=None):
+    """A fresh r_sqrt_sigma, fp64 (label_dim, z_dim) on ``device``, uniform in
+    +-sqrt(6 / (label_dim + z_dim)): what the reference's loops draw every step
+    under ``residue_sigma == "random"`` (fairsoft_train.py:60-66, :247-253;
+    fairsoft_train_postprocess.py:97-103; train.py:120, :351).  ``out``: the
+    tensor to fill (contiguous, that shape, dtype and device) and return.
+
+    ``args.mpvae_r_draw`` selects the source:
+      "numpy"   the reference's line itself: ``np.random.uniform`` on numpy's
+                global stream, then the upload -- its values and its stream
+                position, on CPU or GPU tensors; the host draws and the device
+                waits for the copy;
+      "philox"  mpv_r_uniform_philox (include/mpvae_hip.h): the same
+                distribution from the device Philox stream keyed by
+                ``args.mpvae_seed`` (an int, or the one-element int64 device
+                tensor the probit noise reads) at offset 0, in a counter domain
+                the noise never uses.  No host wait, capturable; GPU only."""
+    mode = getattr(args, "mpvae_r_draw", None)
+    if mode not in R_DRAWS:
+        raise ValueError(f"args.mpvae_r_draw must be one of {R_DRAWS} to draw r_sqrt_sigma "
+                         f"(got {mode!r})")
+    device = torch.device(device)
+    L, z = int(args.label_dim), int(args.z_dim)
+    if out is not None and (tuple(out.shape) != (L, z) or out.dtype != torch.float64
+                            or out.device.type != device.type or not out.is_contiguous()
+                            or (device.index is not None and out.device != device)):
+        raise ValueError(f"out must be a contiguous float64 {(L, z)} tensor on {device} (got "
+                         f"{out.dtype} {tuple(out.shape)} on {out.device})")
+    if mode == "numpy":
+        r_sqrt_sigma = torch.from_numpy(
+            np.random.uniform(-np.sqrt(6.0 / (args.label_dim + args.z_dim)),
+                              np.sqrt(6.0 / (args.label_dim + args.z_dim)),
+                              (args.label_dim, args.z_dim))).to(device)
+        return r_sqrt_sigma if out is None else out.copy_(r_sqrt_sigma)
+    if device.type != "cuda":
+        raise ValueError("args.mpvae_r_draw = 'philox' draws on the GPU; CPU tensors take the "
+                         "reference's 'numpy' draw")
+    seed = getattr(args, "mpvae_seed", None)
+    if seed is None:
+        raise ValueError("args.mpvae_r_draw = 'philox' needs args.mpvae_seed: an int, or the "
+                         "one-element int64 device tensor the probit noise reads")
+    if out is None:
+        out = torch.empty((L, z), dtype=torch.float64, device=device)
+    dev_key = isinstance(seed, torch.Tensor)
+    HipShardBackend._check_seed(seed, out.device)
+    mpvae_hip.check(mpvae_hip.load_library().mpv_r_uniform_philox(
+        L, z, float(np.sqrt(6.0 / (L + z))), 0 if dev_key else int(seed) & (2 ** 64 - 1),
+        mpvae_hip.ptr(seed) if dev_key else None, 0, mpvae_hip.ptr(out),
+        mpvae_hip.stream_of(out.device)), "mpv_r_uniform_philox")
+    return out
 
 
 class VAE(nn.Module):

@@ -206,6 +206,16 @@ def split_samples(n_sample, world, rank):
     return S_local, s_offset
 
 
+def exchange_active(args, group=None):
+    """Whether shard_for gives this process an exchange: args.mpvae_shard in an
+    initialised process group of more than one rank (or of one, with
+    args.mpvae_force_exchange)."""
+    if not getattr(args, "mpvae_shard", False) or not dist.is_available() \
+            or not dist.is_initialized():
+        return False
+    return dist.get_world_size(group) > 1 or bool(getattr(args, "mpvae_force_exchange", False))
+
+
 def shard_for(args, n_sample, group=None):
     """This rank's slice of the sample axis (the whole axis unless args.mpvae_shard).
     args.mpvae_force_exchange runs the collectives even on a world of one (a
@@ -214,12 +224,9 @@ def shard_for(args, n_sample, group=None):
     the process, True on every call, an int k > 1 on every k-th call, False
     never."""
     global _SHARDED_CALLS
-    if not getattr(args, "mpvae_shard", False) or not dist.is_available() \
-            or not dist.is_initialized():
+    if not exchange_active(args, group):
         return Shard(n_sample, 0, None)
     world, rank = dist.get_world_size(group), dist.get_rank(group)
-    if world == 1 and not getattr(args, "mpvae_force_exchange", False):
-        return Shard(n_sample, 0, None)
     if n_sample < world:
         raise ValueError(f"n_sample={n_sample} cannot be sharded over {world} ranks")
     S_local, s_offset = split_samples(n_sample, world, rank)

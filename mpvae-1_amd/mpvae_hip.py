@@ -123,7 +123,8 @@ KERNELS = ["noise_philox", "split", "probit_fwd", "fwd_combine", "finalize", "bw
            "kl_bwd", "label_weights", "label_sim", "group_rows", "fair_fwd", "fair_bwd", "metrics", "linear", "adam",
            "adam_finish", "curve_keys", "curve_sort", "curve_merge", "curve_pass", "curve_agg",
            "metric_sweep", "calib_fwd", "calib_tables", "calib_bwd", "probit_predict",
-           "predict_final", "split_eval", "split_final", "gather_batch", "philox_raw"]
+           "predict_final", "split_eval", "split_final", "gather_batch", "philox_raw",
+           "r_uniform"]
 
 
 def kernel_times():

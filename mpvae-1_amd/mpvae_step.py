@@ -528,12 +528,33 @@ def step_args(args, advance_seed=True):
     return args
 
 
-def _need_device_philox(args, who):
-    """A capture draws its noise on the device, from a key it reads there."""
+def _need_device_philox(args, who, r_draw=False):
+    """A capture draws its noise (``r_draw``: and its per-step r_sqrt_sigma) on
+    the device, from a key it reads there."""
     if getattr(args, "mpvae_noise", "torch_cpu") != "philox" or not isinstance(
             getattr(args, "mpvae_seed", None), torch.Tensor):
         raise ValueError(f"{who} needs args.mpvae_noise = 'philox' and a one-element int64 "
-                         "device tensor as args.mpvae_seed")
+                         "device tensor as args.mpvae_seed"
+                         + (" (args.mpvae_r_draw = 'philox' draws r_sqrt_sigma from the key the "
+                            "noise reads, on the device at every replay)" if r_draw else ""))
+
+
+def _r_draw_mode(args):
+    """args.mpvae_r_draw as the steps take it: None (absent: the model's
+    r_sqrt_sigma, no draw), "numpy" or "philox" (mpvae.draw_r_sqrt_sigma).  The
+    reference redraws r_sqrt_sigma under residue_sigma == "random" alone."""
+    import mpvae
+    mode = getattr(args, "mpvae_r_draw", None)
+    if mode is None:
+        return None
+    if mode not in mpvae.R_DRAWS:
+        raise ValueError(f"args.mpvae_r_draw must be None or one of {mpvae.R_DRAWS} "
+                         f"(got {mode!r})")
+    if getattr(args, "residue_sigma", None) != "random":
+        raise ValueError(f"args.mpvae_r_draw = {mode!r} needs args.residue_sigma = 'random' (got "
+                         f"{getattr(args, 'residue_sigma', None)!r}): the model's r_sqrt_sigma is "
+                         "trainable or zero there, and the reference never redraws it")
+    return mode
 
 
 def _need_capturable(opt, who):
@@ -565,7 +586,22 @@ class TrainStep(_Capturing):
     order, and that ``run_epoch`` gathers from a ``DeviceSplit``; a subclass
     with a third input declares it there and writes ``_body(self, label, feat,
     sens)``.  ``params`` (default: the model's trainable parameters) are the
-    tensors the optimizer steps."""
+    tensors the optimizer steps.
+
+    r_sqrt_sigma is the model's.  Under ``residue_sigma == "random"`` the
+    reference's loops draw a fresh one every step instead (fairsoft_train.py:
+    60-69, train.py:120); ``args.mpvae_r_draw`` (absent / None: off) reproduces
+    that, between the model forward and the loss, into ``r_drawn`` (fp64,
+    allocated once), which compute_loss then takes without a gradient:
+      "numpy"   ``np.random.uniform`` on the global numpy stream and an upload,
+                the reference's line -- its values and stream position bit for
+                bit; the step waits for the host, so ``capture()`` refuses it;
+      "philox"  one mpv_r_uniform_philox launch keyed by ``args.mpvae_seed``: the
+                same distribution from another stream (not numpy's bits); with
+                a device seed the finalize launch advances the key afterwards,
+                so every step and every replay of a captured step draws anew.
+    Any other ``residue_sigma``, and an active ``args.mpvae_shard`` exchange
+    (every rank would need the same draw), raise ValueError."""
 
     inputs = ("label", "feat")
 
@@ -585,6 +621,13 @@ class TrainStep(_Capturing):
         self.updates = torch.zeros((), dtype=torch.int64, device=dev)  # applied updates
         self.found_inf = torch.zeros((), dtype=torch.float32, device=dev)  # the gate's flag
         self._one = torch.ones((), dtype=torch.float32, device=dev)
+        # args.mpvae_r_draw: every step's r_sqrt_sigma is drawn into r_drawn (one
+        # buffer for the step's life, so a captured draw has a static address)
+        self.r_draw = _r_draw_mode(args)
+        self.r_drawn = None
+        if self.r_draw is not None:
+            self.r_drawn = torch.empty((int(args.label_dim), int(args.z_dim)),
+                                       dtype=torch.float64, device=model.r_sqrt_sigma.device)
         self._drop_graphs()
         self.sched = None
         if scheduler is not None:
@@ -631,13 +674,39 @@ class TrainStep(_Capturing):
         for dt, grads in by_dtype.items():
             torch._foreach_mul_(grads, coef.to(dt))
 
+    def _r_sqrt_sigma(self):
+        """The r_sqrt_sigma of this step's compute_loss, taken between the model
+        forward and the loss as the reference takes it (fairsoft_train.py:57-69):
+        the model's, or with ``args.mpvae_r_draw`` a fresh draw into ``r_drawn``
+        (no gradient: the frozen-R backward runs, and the model's own
+        r_sqrt_sigma is neither read nor written)."""
+        if self.r_draw is None:
+            return self.model.r_sqrt_sigma
+        import mpvae
+        import mpvae_dist
+        if mpvae_dist.exchange_active(self.args):
+            raise ValueError(f"args.mpvae_r_draw = {self.r_draw!r} with an active args.mpvae_shard "
+                             "exchange: every rank would have to draw the same r_sqrt_sigma, "
+                             "which the sharded step does not arrange")
+        return mpvae.draw_r_sqrt_sigma(self.args, self.r_drawn.device, out=self.r_drawn)
+
+    def _need_capturable_draw(self, who):
+        """A captured step's r_sqrt_sigma draw runs on the device too."""
+        if self.r_draw == "numpy":
+            raise ValueError(f"{who}: args.mpvae_r_draw = 'numpy' draws r_sqrt_sigma on the host "
+                             "every step, which a HIP graph cannot contain; 'philox' draws on "
+                             "the device")
+        if self.r_draw == "philox":
+            _need_device_philox(self.args, who, r_draw=True)
+
     def _objective(self, label, feat):
         """Forward and loss: ``(the tensor to backpropagate, the step's
         outputs)``.  Here compute_loss's total and its 8 outputs; a subclass
         adds its terms (FairTrainStep)."""
         import mpvae
         out = self.model(label, feat)
-        res = mpvae.compute_loss(label, *out, self.model.r_sqrt_sigma, step_args(self.args, self.advance_seed))
+        res = mpvae.compute_loss(label, *out, self._r_sqrt_sigma(),
+                                 step_args(self.args, self.advance_seed))
         return res[0], res
 
     def _body(self, *batch):
@@ -710,6 +779,7 @@ class TrainStep(_Capturing):
         must be built with ``capturable=True`` (its step counter and bias
         corrections then live on the device)."""
         self._check_batch(batch)
+        self._need_capturable_draw("capture()")
         _need_capturable(self.opt, "capture()")
         self._captured = _Captured(self._body, [t.clone() for t in batch], warmup,
                                    lambda: self.opt.zero_grad(set_to_none=True))
@@ -764,6 +834,7 @@ class TrainStep(_Capturing):
         holds a full batch.  ``capture()`` and ``__call__`` keep their own graph
         and buffers."""
         B = int(batch_size)
+        self._need_capturable_draw("capture_epoch()")
         _need_capturable(self.opt, "capture_epoch()")
         _need_device_philox(self.args, "capture_epoch()")
         if split.device.type != "cuda" or split.device != self.params[0].device:
@@ -815,8 +886,10 @@ class CalibrationStep(TrainStep):
       the reference's own backward through them fed nothing that was read;
     * the reference accumulates model gradients that it never clears or reads;
       the step produces none;
-    * r_sqrt_sigma is the model's (the reference's ``residue_sigma ==
-      "random"`` host draw is not reproduced, as in TrainStep).
+    * r_sqrt_sigma is the model's unless ``args.mpvae_r_draw`` is set; with it
+      the reference's ``residue_sigma == "random"`` per-step draw
+      (fairsoft_train_postprocess.py:97-106) is reproduced as in TrainStep:
+      bit for bit under "numpy", in distribution under "philox".
 
     The optimizer must be a plain fused ``torch.optim.Adam([threshold_], ...,
     fused=True)`` (it steps in ``adam_step``), with ``capturable=True`` for
@@ -841,7 +914,7 @@ class CalibrationStep(TrainStep):
         args = step_args(self.args, self.advance_seed)
         with torch.no_grad():
             out = self.model(label, feat)
-            res = mpvae.compute_loss(label, *out, self.model.r_sqrt_sigma, args)
+            res = mpvae.compute_loss(label, *out, self._r_sqrt_sigma(), args)
         bce, fair, cal_prob, active, contributed = mpvae_fair.calibration_loss(
             res[6], self.threshold_, label, sens, self.centroids, self.tables, args.learn_logit)
         cal_total = fair * args.fair_coeff + bce
@@ -909,8 +982,10 @@ class FairTrainStep(TrainStep):
     ``validate()`` is the body of validate_mpvae_softfair with sums of its own.
 
     Differences from the reference:
-    * r_sqrt_sigma is the model's (the ``residue_sigma == "random"`` per-step
-      host draw is not reproduced, as in TrainStep);
+    * r_sqrt_sigma is the model's unless ``args.mpvae_r_draw`` is set; with it
+      the ``residue_sigma == "random"`` per-step draw (:60-69; ``validate``:
+      :247-256) is reproduced as in TrainStep: bit for bit under "numpy", in
+      distribution under "philox";
     * ``fairloss`` is always a tensor, zero when no term is active (the
       reference's Python float 0., which it does not add);
     * the penalty arithmetic is fp64 whatever the distance values are
@@ -936,7 +1011,8 @@ class FairTrainStep(TrainStep):
         import mpvae
         import mpvae_fair
         out = self.model(label, feat)
-        res = mpvae.compute_loss(label, *out, self.model.r_sqrt_sigma, step_args(self.args, self.advance_seed))
+        res = mpvae.compute_loss(label, *out, self._r_sqrt_sigma(),
+                                 step_args(self.args, self.advance_seed))
         fair, contributed = mpvae_fair.fairness_penalty(
             res[7], res[6], label, sens, self.tables, norm, self.args.fair_coeff,
             max_groups=self.max_groups, fused=self.fused)
